@@ -2,10 +2,17 @@
 """Headline benchmark: brute-force cosine / L2 top-k on MI355X (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5|c6] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one batch of queries searched against the whole corpus (fused
 MFMA candidate scan + exact fp64 rerank; queries, corpus and outputs resident
-in HBM).  The default run measures BASELINE.json's metric, both halves:
+in HBM).  A plain run does what the headline figure needs and no more: it builds
+the config's index (default c2), warms up, times the K steps, writes the last
+timed step's outputs if --dump-outputs is given, and prints the result line
+(QPS, ms_per_step).  Everything below that is not that figure -- the sub-records,
+p50 latency, rooflines that need a loop of their own, recall, CPU baselines,
+serving numbers -- is measured with --full only.
+The --full default run measures BASELINE.json's metric, both halves:
   * the line itself: configs[1] (C2: 1M x 768 cosine top-10, batch 64) -- at
     N > 1 row-sharded with the batch per GPU fixed ("weak": global batch 64 N);
   * "metric_workload_10m_x_128": the metric's "10M x 128D @8 GPU" workload (c6:
@@ -19,8 +26,9 @@ the others to "weak".
 
 Throughput (`value`): the K timed batches are queued back to back on the stream
 (device-memory searches return without a host wait) between two synchronises;
-latency (`p50_ms`) comes from a separate loop that waits for every batch.
-Rank 0 prints one JSON line: QPS (whole job), p50 batch latency, the roofline
+latency (`p50_ms`, --full) comes from a separate loop that waits for every batch.
+Rank 0 prints one JSON line: QPS (whole job) and `ms_per_step`, the wall time of
+one timed step; with --full also the p50 batch latency, the roofline
 of the dominant kernel (the scan kernel, HIP-event timed inside the library on
 the stream it runs on; named against the implementation's own work and against
 SURVEY.md §8(d)'s) and, at N=1, the CPU baseline: the reference's paths restated
@@ -239,6 +247,16 @@ def cpu_graph_baseline(V, nbr, entries, Q, k, ef, metric, gt, budget_s=15.0):
             "recall_at_10": hits / float(n * k)}
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the last timed step returned to its caller, one DIR/<name>.npy per
+    device array (scores as they are, fp32; row ids as fp64, exact below 2^53).  The inputs are
+    seeded, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 def bench_graph(args, world, rank, local, dev, primary=True):
     """C5: the graph path at batch 1.  N>1 runs independent replicas (SURVEY.md §8e:
     each GPU holds the whole graph and serves its own queries); value = all queries
@@ -256,7 +274,7 @@ def bench_graph(args, world, rank, local, dev, primary=True):
     knn = args.graph_knn or R
     ix = _vdb.NativeIndex(D, metric, local)
     ix.reserve(N)
-    keep_host = world == 1 and rank == 0 and not args.no_cpu_baseline
+    keep_host = args.full and world == 1 and rank == 0 and not args.no_cpu_baseline
     parts = []
     clustered = args.data == "clustered" and primary
     cen = cluster_centres(D) if clustered else None
@@ -312,38 +330,42 @@ def bench_graph(args, world, rank, local, dev, primary=True):
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     iters = (g.stat("iterations") - it0) / args.steps
     visited = (g.stat("visited") - vis0) / args.steps
-    # recall@10 of the timed queries against the exact brute-force path
-    Qt = Q[args.warmup:]
-    _, gt = ix.search(Qt, k)
-    got = lab[args.warmup:].cpu().numpy()
-    recall = sum(len(set(a.tolist()) & set(b.tolist())) for a, b in zip(got, gt)) / float(gt.size)
-    # exact brute force at batch 1 for comparison (same queries, device resident)
-    os_, oi_ = torch.empty((1, k), device=dev), torch.empty((1, k), dtype=torch.int64, device=dev)
-    for i in range(3):
-        ix.search_device(q_dev[i].data_ptr(), 1, k, os_.data_ptr(), oi_.data_ptr(), 0, stream=sp)
-    torch.cuda.synchronize()
-    bl = []
-    for i in range(min(args.steps, 50)):
-        t1 = time.perf_counter()
-        ix.search_device(q_dev[i].data_ptr(), 1, k, os_.data_ptr(), oi_.data_ptr(), 0, stream=sp)
+    if primary and args.dump_outputs and rank == 0:  # the last timed query's labels and distances
+        last = args.warmup + args.steps - 1
+        dump_outputs(args.dump_outputs, {"labels": lab[last], "distances": dst[last]})
+    if args.full:
+        # recall@10 of the timed queries against the exact brute-force path
+        Qt = Q[args.warmup:]
+        _, gt = ix.search(Qt, k)
+        got = lab[args.warmup:].cpu().numpy()
+        recall = sum(len(set(a.tolist()) & set(b.tolist())) for a, b in zip(got, gt)) / float(gt.size)
+        # exact brute force at batch 1 for comparison (same queries, device resident)
+        os_, oi_ = torch.empty((1, k), device=dev), torch.empty((1, k), dtype=torch.int64, device=dev)
+        for i in range(3):
+            ix.search_device(q_dev[i].data_ptr(), 1, k, os_.data_ptr(), oi_.data_ptr(), 0, stream=sp)
         torch.cuda.synchronize()
-        bl.append(time.perf_counter() - t1)
-    # the same queries at other team counts (p50 over <= 100 single queries, recall)
-    sweep = []
-    for tm in [int(x) for x in (args.teams_sweep if primary else "").split(",") if x.strip()]:
-        if tm == args.teams:
-            continue
-        g.set_param("teams", tm)
-        tl = []
-        for j in range(min(args.steps, 100)):
+        bl = []
+        for i in range(min(args.steps, 50)):
             t1 = time.perf_counter()
-            one(args.warmup + j)
+            ix.search_device(q_dev[i].data_ptr(), 1, k, os_.data_ptr(), oi_.data_ptr(), 0, stream=sp)
             torch.cuda.synchronize()
-            tl.append(time.perf_counter() - t1)
-        gl = lab[args.warmup:args.warmup + len(tl)].cpu().numpy()
-        rc = sum(len(set(a.tolist()) & set(b.tolist())) for a, b in zip(gl, gt[:len(tl)])) / float(len(tl) * k)
-        sweep.append({"teams": tm, "p50_ms": float(np.median(tl)) * 1e3, "recall_at_10": rc})
-    g.set_param("teams", args.teams)
+            bl.append(time.perf_counter() - t1)
+        # the same queries at other team counts (p50 over <= 100 single queries, recall)
+        sweep = []
+        for tm in [int(x) for x in (args.teams_sweep if primary else "").split(",") if x.strip()]:
+            if tm == args.teams:
+                continue
+            g.set_param("teams", tm)
+            tl = []
+            for j in range(min(args.steps, 100)):
+                t1 = time.perf_counter()
+                one(args.warmup + j)
+                torch.cuda.synchronize()
+                tl.append(time.perf_counter() - t1)
+            gl = lab[args.warmup:args.warmup + len(tl)].cpu().numpy()
+            rc = sum(len(set(a.tolist()) & set(b.tolist())) for a, b in zip(gl, gt[:len(tl)])) / float(len(tl) * k)
+            sweep.append({"teams": tm, "p50_ms": float(np.median(tl)) * 1e3, "recall_at_10": rc})
+        g.set_param("teams", args.teams)
     p50 = float(np.median(lat))
     if world > 1:
         t = torch.tensor([elapsed, p50, kern_ms], dtype=torch.float64, device=dev)
@@ -364,7 +386,6 @@ def bench_graph(args, world, rank, local, dev, primary=True):
             "ms_per_step": elapsed / args.steps * 1e3,
             "p50_ms": p50 * 1e3,
             "p99_ms": float(np.percentile(lat, 99)) * 1e3,
-            "recall_at_10": recall,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -381,14 +402,14 @@ def bench_graph(args, world, rank, local, dev, primary=True):
             "build_s": build_s,
             "iterations_per_query": iters,
             "visited_per_query": visited,
-            "exact_b1_p50_ms": float(np.median(bl)) * 1e3,
-            "teams_sweep": sweep,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel": "graph_search",
                          "avg_launch_ms": kern_ms, "algorithmic_bytes": q_bytes,
                          "note": f"{args.teams} workgroups per query, each a chain of dependent beam steps: "
                                  "latency-bound, not bandwidth-bound"},
         }
+        if args.full:
+            rec.update(recall_at_10=recall, exact_b1_p50_ms=float(np.median(bl)) * 1e3, teams_sweep=sweep)
         if keep_host:
             V = np.concatenate(parts) if len(parts) > 1 else parts[0]
             del parts
@@ -440,14 +461,22 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
-                    help="default: c2 (BASELINE.json configs[1]) plus the metric's 8-GPU workload c6 as a sub-record")
+                    help="default: c2 (BASELINE.json configs[1]); with --full plus the metric's 8-GPU workload c6 "
+                         "and c3 / c4 / c5 as sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline figure: p50 latency, the scan's roofline from a loop "
+                         "of its own, CPU baselines, serving numbers, c5's recall and sweeps and, without --config, "
+                         "the c6 / c3 / c4 / c5 sub-records (the --no-* options below trim a --full run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last timed step's outputs as DIR/<name>.npy "
+                         "(scores.npy fp32 and indices.npy fp64; c5: distances.npy and labels.npy)")
     ap.add_argument("--no-metric-workload", action="store_true",
-                    help="default run: skip the c6 sub-record (the metric's 10M x 128 workload)")
+                    help="--full default run: skip the c6 sub-record (the metric's 10M x 128 workload)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run: skip the c3 / c4 sub-records (BASELINE.json configs[2], [3])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full default run: skip the c3 / c4 sub-records (BASELINE.json configs[2], [3])")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-serving", action="store_true",
-                    help="c1/c2 at N=1: skip the store-API serving numbers (batch-1 p50, 4-thread QPS)")
+                    help="--full, c1/c2 at N=1: skip the store-API serving numbers (batch-1 p50, 4-thread QPS)")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="N>1: weak = global batch B*N (fixed work per GPU), strong = global batch B "
                          "(default: strong for c4 / c6, whose BASELINE batch is sharded, weak otherwise)")
@@ -496,7 +525,7 @@ def main():
     ap.add_argument("--graph-entries", type=int, default=None,
                     help="c5: entry rows of the graph (default performance/hnsw_index.py N_ENTRIES)")
     ap.add_argument("--teams-sweep", default="16,64", help="c5: extra teams settings reported beside the line")
-    ap.add_argument("--no-graph", action="store_true", help="default run: skip the c5 (graph) sub-record")
+    ap.add_argument("--no-graph", action="store_true", help="--full default run: skip the c5 (graph) sub-record")
     ap.add_argument("--data", default="uniform", choices=["uniform", "clustered"],
                     help="c5: the corpus (BASELINE's uniform [0,1) rows, or rows around cluster centres: the "
                          "structured data a graph index is for)")
@@ -504,6 +533,8 @@ def main():
                     help="HBM traffic of the scan kernel from a separate rocprofv3 --pmc pass "
                          "(default: newest profiles/*/pmc.json for this config, see profiles/scripts/)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus != world:
@@ -525,8 +556,8 @@ def main():
         rec = bench_graph(args, world, rank, local, dev)
     else:
         rec = bench_brute(cfg, args, world, rank, local, dev, primary=True)
-    if args.config is None:
-        # The default run also measures, on the same ranks, as compact sub-records (so the driver's
+    if args.config is None and args.full:
+        # The --full default run also measures, on the same ranks, as compact sub-records (so the driver's
         # N = 1, 2, 4, 8 series carries them all):
         #   c6, the second half of BASELINE.json's metric, "10M x 128D @8 GPU" (cosine top-10,
         #       batch 64, row-sharded with the batch fixed);
@@ -580,7 +611,7 @@ def bench_brute(cfg, args, world, rank, local, dev, primary=True):
 
     # ---- data: this rank's shard of the corpus, replicated queries -------------------
     # (every record at N = 1 carries its CPU baseline, VERDICT r5 #4: sub-records on a shorter budget)
-    keep_host = world == 1 and rank == 0 and not args.no_cpu_baseline
+    keep_host = args.full and world == 1 and rank == 0 and not args.no_cpu_baseline
     ix = _vdb.NativeIndex(D, metric, local, precision=args.precision)
     if args.scan_variant is not None:
         ix.set_param("scan_variant" if args.precision == "fp32" else "scan_variant_bf16x3", args.scan_variant)
@@ -691,6 +722,9 @@ def bench_brute(cfg, args, world, rank, local, dev, primary=True):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
+    if primary and args.dump_outputs and rank == 0:  # the last timed step's output buffers
+        ls_, li_ = outs[(n_step[0] - 1) % n_str]
+        dump_outputs(args.dump_outputs, {"scores": ls_, "indices": li_})
     n_t = ix.stat("timed_searches") - n0
     # candidate passes per arithmetic in the timed region (precision "auto" picks per search)
     by_prec = {p: ix.stat(f"searches_{p}") - by_prec0[p] for p in by_prec0}
@@ -699,7 +733,8 @@ def bench_brute(cfg, args, world, rank, local, dev, primary=True):
     scan_ms = (ix.stat("scan_ns") - scan0) / 1e6 / max(n_t, 1)
     pipe_ms = (ix.stat("pipeline_ns") - pipe0) / 1e6 / max(n_t, 1)
     roof_timing = "hip events in the timed loop"
-    if not ev_in_loop:  # the scan's launch time from a second run of the loop on one stream
+    have_scan_ms = ev_in_loop or args.full
+    if not ev_in_loop and args.full:  # the scan's launch time from a second run of the loop on one stream
         roof_timing = "hip events in a one-stream rerun of the timed loop (no events in the timed loop)"
         n_str = 1
         ix.set_param("timing", 1)
@@ -711,14 +746,15 @@ def bench_brute(cfg, args, world, rank, local, dev, primary=True):
         scan_ms = (ix.stat("scan_ns") - scan0) / 1e6 / max(n_t, 1)
         pipe_ms = (ix.stat("pipeline_ns") - pipe0) / 1e6 / max(n_t, 1)
     ix.set_param("timing", 0)
-    # Latency (p50_ms): one batch at a time, each waited for
+    # Latency (p50_ms, --full): one batch at a time, each waited for
     n_str = 1
     lat = []
-    for _ in range(min(args.steps, 50)):
+    for _ in range(min(args.steps, 50) if args.full else 0):
         t0 = time.perf_counter()
         step()
         torch.cuda.synchronize()
         lat.append(time.perf_counter() - t0)
+    lat = lat or [0.0]  # (a plain run: no latency loop, no p50_ms in the line)
     if world > 1:
         t = torch.tensor([elapsed, scan_ms, pipe_ms, float(np.median(lat))], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -728,7 +764,7 @@ def bench_brute(cfg, args, world, rank, local, dev, primary=True):
 
     fallback = ix.stat("fallback_queries")
     overflow = ix.stat("overflow_queries")
-    if rank == 0:
+    if rank == 0 and have_scan_ms:
         # Two rooflines of the scan kernel, each named:
         # (1) "implementation" (the top-level fields): the work the kernel's own arithmetic must do
         #     per launch -- every corpus row read once at the element size of the candidate copy it
@@ -790,6 +826,7 @@ def bench_brute(cfg, args, world, rank, local, dev, primary=True):
                 traffic = pm["hbm_bytes_per_launch"]
                 traffic_src = os.path.relpath(path, ROOT)
                 break
+    if rank == 0:
         rec = {
             "metric": METRIC,
             "value": Bg * args.steps / elapsed,
@@ -798,7 +835,6 @@ def bench_brute(cfg, args, world, rank, local, dev, primary=True):
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "p50_ms": p50 * 1e3,
             "higher_is_better": True,
             "scaling": scaling if world > 1 else "weak",
             "vs_baseline": None,
@@ -812,20 +848,23 @@ def bench_brute(cfg, args, world, rank, local, dev, primary=True):
                        "batch_per_gpu_equiv": B, "k": k,
                        "metric": metric, "parallelism": f"row-shard x{world}" if world > 1 else "single GPU",
                        "rows_per_gpu": n_local},
-            "roofline": dict(roof, traffic=traffic,
-                             kernel=kname,
-                             fp32_equivalent=fp32_eq, precision=prec,
-                             precision_requested=args.precision, searches_by_precision=by_prec,
-                             traffic_source=traffic_src, algorithmic_bytes=hbm_bytes, algorithmic_flops=mfma_flops,
-                             avg_launch_ms=scan_ms, hbm_gbs=achieved_gbs, mfma_tflops=achieved_tf,
-                             hbm_frac=achieved_gbs / HBM_PEAK_GBS, mfma_frac=achieved_tf / mfma_peak),
-            "pipeline_ms": pipe_ms,
             "streams": max(1, args.streams),
-            "roofline_timing": roof_timing,
             "fallback_queries_total": fallback,
             "fallback_queries_timed": fb_timed,  # (auto's bf16 probe falls back in warm-up at C3 / C4)
             "fallback_list_overflow": overflow,
         }
+        if args.full:
+            rec["p50_ms"] = p50 * 1e3
+        if have_scan_ms:
+            rec["roofline"] = dict(roof, traffic=traffic,
+                                   kernel=kname,
+                                   fp32_equivalent=fp32_eq, precision=prec,
+                                   precision_requested=args.precision, searches_by_precision=by_prec,
+                                   traffic_source=traffic_src, algorithmic_bytes=hbm_bytes, algorithmic_flops=mfma_flops,
+                                   avg_launch_ms=scan_ms, hbm_gbs=achieved_gbs, mfma_tflops=achieved_tf,
+                                   hbm_frac=achieved_gbs / HBM_PEAK_GBS, mfma_frac=achieved_tf / mfma_peak)
+            rec["pipeline_ms"] = pipe_ms
+            rec["roofline_timing"] = roof_timing
         if keep_host:
             V = np.concatenate(host_parts) if len(host_parts) > 1 else host_parts[0]
             del host_parts
