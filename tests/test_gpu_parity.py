@@ -57,6 +57,8 @@ def _check(vdb, V, Q, k, metric, mask=None, force_exact=False, margin=None, chun
     # fp64 keys: bit-exact with the canonical order
     np.testing.assert_array_equal(kk[valid], ek[valid])
     np.testing.assert_array_equal(s[valid], es[valid])
+    # |approx - exact| <= eps and the int8 checksum are invariants of an honest pass on any data
+    assert ix.stat("inconsistent_queries") == 0
     return ix, s, i
 
 

@@ -36,6 +36,8 @@ def _search_check(ix, Q, V, k, metric, mask=None):
     valid = ei >= 0
     np.testing.assert_array_equal(kk[valid], ek[valid])
     np.testing.assert_array_equal(s[valid], es[valid])
+    # |approx - exact| <= eps and the int8 checksum are invariants of an honest pass on any data
+    assert ix.stat("inconsistent_queries") == 0
 
 
 @pytest.mark.parametrize("precision", ["i8q", "i8x3", "i8", "auto"])
