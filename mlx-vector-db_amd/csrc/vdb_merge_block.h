@@ -54,7 +54,8 @@ __device__ __attribute__((noinline)) void head_threshold(const K* Lq, const I* I
     }
 }
 
-// Sort c (<= 64 E) LDS entries with a register network, store the first n_out.
+// Sort c (<= 64 E) LDS entries with a register network, store the first n_out; slots
+// [64 E, n_out) get the sentinel (the network holds 64 E entries, n_out may be larger).
 template <typename K, typename I, int E>
 __device__ __attribute__((noinline)) void sort_store_prefix(const K* bk, const I* bi, int c, int n_out, K* ok,
                                                             I* oi) {
@@ -76,6 +77,10 @@ __device__ __attribute__((noinline)) void sort_store_prefix(const K* bk, const I
             oi[e] = x[i];
         }
     }
+    for (int e = 64 * E + lane; e < n_out; e += 64) {
+        ok[e] = (K)-INFINITY;
+        oi[e] = sentinel_idx<I>();
+    }
 }
 
 // LDS bytes merge_block needs (dynamic; the caller's buffer at smem).
@@ -87,6 +92,10 @@ __host__ __device__ inline size_t merge_block_lds(int KP) {
 
 // The merge of one query's lists (Lq / Iq: list j at j * sj) by one 256-thread workgroup
 // into okq / oiq (KP entries); all 256 threads call it.
+// Postcondition: every one of the KP slots of okq / oiq is written, whatever the number of valid
+// entries: the best min(valid, KP) sorted (key desc, row asc), then (-inf, sentinel).  The
+// callers' output buffers are uninitialised scratch and their readers take the first k <= KP
+// slots as they are (finalize_kernel, the fused tail of exact_scan_kernel, topk_write_kernel).
 template <typename K, typename I>
 __device__ void merge_block(const K* __restrict__ Lq, const I* __restrict__ Iq, int n_lists, int Lk, int64_t sj,
                             int KP, K* __restrict__ okq, I* __restrict__ oiq, char* smem) {
