@@ -166,6 +166,23 @@ int32_t vdb_index_add(vdb_index* idx, const float* vectors, int64_t n, int32_t m
 int32_t vdb_index_count(const vdb_index* idx, int64_t* n);
 /* Replaces MLXVectorStore.clear (service/optimized_vector_store.py:198-209). */
 int32_t vdb_index_clear(vdb_index* idx);
+/* Remove the rows whose bit is set in remove_mask (ceil(count/32) uint32 words, bit r of word
+ * r/32 = row r; same layout and memory kinds as the search's row_mask; bits at or past
+ * count are ignored).  Surviving rows keep their order and move down: row r becomes
+ * r - (removed rows below r).  *n_removed (optional) = rows removed.  Returns when done.
+ * Replaces: nothing in the reference server, which cannot delete; the counterpart is its
+ * Python SDK's delete_vectors_by_metadata (sdk/python/mlx_vector_db_client.py:292-303,
+ * POST /vectors/delete).  The rows are compacted on the device (a stable gather driven by the
+ * bitmap, DESIGN.md "Deleting rows") and the candidate copies of the moved rows rebuilt from
+ * them with the centring row, quantisation step and residual direction left as they are; the
+ * capacity stays.  Waits for the searches queued on this index first; a device-memory mask is
+ * read after the work queued on `stream`.  A mask with no bit set below count touches nothing;
+ * one that removes every row leaves the index as a clear does.  Knob "remove_chunk" (rows per
+ * chunk of the gather's scratch, 0 = sized by bytes); stat "rows_removed" (cumulative).  A
+ * graph built before a remove or a clear is stale for good (search and add report it), even
+ * once later adds bring the count back. */
+int32_t vdb_index_remove(vdb_index* idx, const uint32_t* remove_mask, int32_t mem, void* stream,
+                         int64_t* n_removed);
 /* Copy rows [start, start+n) back out, row-major fp32, to host memory (used for
  * vectors.npz persistence, service/optimized_vector_store.py:218-223). */
 int32_t vdb_index_get_vectors(vdb_index* idx, int64_t start, int64_t n, float* out_host);

@@ -8,6 +8,10 @@ and HTTP scripts work unchanged:
   POST /vectors/query         {user_id, model_id, query, k, filter_metadata} (:211-270)
   POST /vectors/batch_query   {user_id, model_id, queries, k}              (:272-330)
   GET  /vectors/count, /vectors/stats, /vectors/health                     (:332-388)
+  POST /vectors/delete        {user_id, model_id, filter_metadata} -> {deleted}: the call the
+                              SDK's delete_vectors_by_metadata makes
+                              (sdk/python/mlx_vector_db_client.py:292-303); the reference
+                              server has no such route
 
 Differences, on purpose:
   * /batch_query works: the reference calls a ``store.batch_query`` that does not exist
@@ -71,6 +75,20 @@ class BatchQueryRequest(BaseModel):
     model_id: str
     queries: List[List[float]]
     k: int = 10
+
+
+class VectorDeleteRequest(BaseModel):
+    """The body the reference's SDK sends (sdk/python/mlx_vector_db_client.py:292-303)."""
+    user_id: str
+    model_id: str
+    filter_metadata: Dict[str, Any] = Field(..., description="Rows whose metadata matches are deleted")
+
+
+class VectorDeleteResponse(BaseModel):
+    success: bool
+    deleted: int
+    total_vectors: int
+    processing_time_ms: float
 
 
 class VectorAddResponse(BaseModel):
@@ -269,6 +287,20 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:  # the reference turns every error, its own 400s included, into a 500
             logger.error("Error in batch query: %s", e)
             raise HTTPException(status_code=500, detail=f"Batch query failed: {e}")
+
+    @router.post("/delete", response_model=VectorDeleteResponse)
+    async def delete_vectors(request: VectorDeleteRequest, api_key: str = Depends(auth)):
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            loop = asyncio.get_running_loop()
+            res = await loop.run_in_executor(mgr._executor,
+                                             lambda: store.delete_vectors(request.filter_metadata))
+            return VectorDeleteResponse(success=True, deleted=res["deleted"], total_vectors=res["total_vectors"],
+                                        processing_time_ms=(time.time() - t0) * 1000)
+        except Exception as e:  # as the sibling routes: every error becomes a 500
+            logger.error("Error deleting vectors: %s", e)
+            raise HTTPException(status_code=500, detail=f"Failed to delete vectors: {e}")
 
     @router.get("/count")
     async def get_vector_count(user_id: str, model_id: str, api_key: str = Depends(auth)):

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/vdb.h"
+#include "vdb_compact_plan.h"
 #include "vdb_internal.h"
 
 using namespace vdb;
@@ -210,10 +211,16 @@ struct vdb_index {
     // the wide int8 pass (vdb_scan8w.hip: rows of 4 groups, B > 256): -1 auto (from kWideMinRows
     // rows), 0 off, 1 at any row count
     int64_t scan_wide = -1;
+    // vdb_index_remove: rows per chunk of the gather's scratch (0 = by bytes, vdb_compact_plan.h)
+    int64_t remove_chunk = 0;
+    // bumped whenever rows leave or move (remove, clear): a graph built before is stale even
+    // when a later add brings the count back to what it recorded
+    std::atomic<int64_t> gen{0};
     // stats
     std::atomic<int64_t> n_searches{0}, n_queries{0}, n_fallback{0}, n_overflow{0}, n_incons{0}, n_repass{0}, n_q4{0};
     std::atomic<int64_t> n_wide{0};  // searches through the wide int8 pass
     std::atomic<int64_t> n_xs_builds{0};  // lazy builds of the split copy (ensure_xs)
+    std::atomic<int64_t> n_rows_removed{0};  // rows removed by vdb_index_remove (cumulative)
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -895,6 +902,10 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
     } else if (n == "i8_narrow") {
         if (value < -1 || value > 0) return set_error(VDB_ERR_INVALID, "i8_narrow must be -1 or 0");
         ix->i8_narrow = value;
+    } else if (n == "remove_chunk") {
+        if (value < 0) return set_error(VDB_ERR_INVALID, "remove_chunk must be >= 0 (0 = sized by bytes)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->remove_chunk = value;
     } else if (n == "device_repass") {
         if (value < -1 || value > 1) return set_error(VDB_ERR_INVALID, "device_repass must be -1, 0 or 1");
         ix->device_repass = value;
@@ -986,6 +997,7 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
         *value = xb + (xs_ptr(ix) ? xb : 0) + (ix->Xq ? xb / 2 : 0) + (ix->Xh ? xb / 4 : 0) + ix->cap_rows * 20;
     } else if (n == "split_copy") *value = xs_ptr(ix) ? 1 : 0;
     else if (n == "split_copy_builds") *value = ix->n_xs_builds.load();
+    else if (n == "rows_removed") *value = ix->n_rows_removed.load();
     else return set_error(VDB_ERR_INVALID, "unknown stat '%s'", name);
     return VDB_OK;
 }
@@ -1174,10 +1186,8 @@ int32_t vdb_index_count(const vdb_index* ix, int64_t* n) {
     return VDB_OK;
 }
 
-int32_t vdb_index_clear(vdb_index* ix) {
-    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
-    HIP_TRY(hipSetDevice(ix->device));
-    std::unique_lock<std::shared_mutex> g(ix->mu);
+// vdb_index_clear under the exclusive lock (also the end of a remove that leaves no row).
+static int32_t clear_locked(vdb_index* ix) {
     {
         const int wr = wait_idle(ix);
         if (wr) return wr;
@@ -1208,6 +1218,152 @@ int32_t vdb_index_clear(vdb_index* ix) {
     ix->dir_set = false;  // the next add picks a new direction (xres_dir's bits were cleared above)
     ix->dir_rows = 0;
     ix->xres_dir = 0.0;
+    ix->gen++;
+    return VDB_OK;
+}
+
+int32_t vdb_index_clear(vdb_index* ix) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::shared_mutex> g(ix->mu);
+    return clear_locked(ix);
+}
+
+int32_t vdb_index_remove(vdb_index* ix, const uint32_t* remove_mask, int32_t mem, void* stream, int64_t* n_removed) {
+    if (n_removed) *n_removed = 0;
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (!remove_mask) return set_error(VDB_ERR_INVALID, "remove_mask is NULL");
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    if (N == 0) return VDB_OK;
+    // queued device-memory searches on caller streams read the buffers the rows move in
+    {
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+    }
+    hipStream_t st = ix->stream;
+    const int64_t n_words = remove_mask_words(N);
+    // one allocation: [the mask's device copy (host masks)] base [n_words + 1], part, info
+    const size_t mask_bytes = mem == VDB_MEM_HOST ? ((size_t)n_words * sizeof(uint32_t) + 255) & ~size_t(255) : 0;
+    char* scan = nullptr;
+    HIP_TRY(hipMalloc(&scan, mask_bytes + remove_scan_bytes(n_words)));
+    RemoveScratch scr{nullptr, nullptr, nullptr, nullptr, nullptr};
+    auto done = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(scan);
+        if (scr.X) (void)hipFree(scr.X);
+        return rc;
+    };
+#define RM_TRY(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t _e = (expr);                                                                        \
+        if (_e != hipSuccess)                                                                          \
+            return done(set_error(_e == hipErrorOutOfMemory ? VDB_ERR_OOM : VDB_ERR_HIP, "remove: %s failed: %s", \
+                                  #expr, hipGetErrorString(_e)));                                      \
+    } while (0)
+    const uint32_t* md = remove_mask;
+    if (mem == VDB_MEM_HOST) {
+        RM_TRY(hipMemcpyAsync(scan, remove_mask, (size_t)n_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        md = reinterpret_cast<const uint32_t*>(scan);
+    } else {
+        // the mask may still be being written on the caller's stream (NULL = the null stream)
+        hipEvent_t ready = nullptr;
+        RM_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(ready, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, ready, 0);
+        (void)hipEventDestroy(ready);
+        RM_TRY(e);
+    }
+    Carver c{scan, mask_bytes};
+    uint32_t* base = c.take<uint32_t>((size_t)n_words + 1);
+    uint32_t* part = c.take<uint32_t>((size_t)((n_words + kScanWgWords - 1) / kScanWgWords));
+    uint32_t* info = c.take<uint32_t>(2);
+    RM_TRY(launch_remove_scan(md, n_words, N, base, part, info, st));
+    uint32_t h_info[2] = {0, 0};
+    RM_TRY(hipMemcpyAsync(h_info, info, sizeof(h_info), hipMemcpyDeviceToHost, st));
+    RM_TRY(hipStreamSynchronize(st));
+    const int64_t kept = (int64_t)h_info[0];
+    if (kept > N || (kept < N && (int64_t)h_info[1] >= n_words))
+        return done(set_error(VDB_ERR_HIP, "remove: inconsistent scan (kept %lld of %lld)", (long long)kept, (long long)N));
+    if (kept == N) return done(VDB_OK);  // no bit set below count: nothing is touched
+    if (kept == 0) {                     // every row: the index is left as a clear leaves it
+        const int rc = done(clear_locked(ix));
+        if (rc == VDB_OK) {
+            ix->n_rows_removed += N;
+            if (n_removed) *n_removed = N;
+        }
+        return rc;
+    }
+    // the gather, chunk by chunk in ascending order from the first word that loses a row
+    const int64_t first_word = (int64_t)h_info[1];
+    const int64_t cw = std::min(remove_chunk_words(ix->remove_chunk, ix->Dp), n_words - first_word);
+    const int64_t crows = cw * 32;
+    {
+        // (each carve starts 256-B aligned: the rows, then the four scalar arrays)
+        const size_t sbytes = (size_t)crows * ((size_t)ix->Dp * sizeof(float) + kRowScalarBytes) + 5 * 256;
+        char* sbuf = nullptr;
+        RM_TRY(hipMalloc(&sbuf, sbytes));
+        Carver s2{sbuf};
+        scr.X = s2.take<float>((size_t)crows * ix->Dp);  // (offset 0: done() frees it through scr.X)
+        scr.nrm64 = s2.take<double>((size_t)crows);
+        scr.inv32 = s2.take<float>((size_t)crows);
+        scr.sq32 = s2.take<float>((size_t)crows);
+        scr.rinit32 = s2.take<float>((size_t)crows);
+    }
+    const RemoveRows rows{ix->X, ix->Dp, ix->nrm64, ix->inv32, ix->sq32, ix->rinit32};
+    const int64_t n_chunks = remove_n_chunks(first_word, n_words, cw);
+    for (int64_t ci = 0; ci < n_chunks; ++ci) {
+        const RemoveChunk k = remove_chunk(first_word, n_words, cw, ci);
+        RM_TRY(launch_remove_chunk(rows, md, base, N, k.w0, k.w1, scr, st));
+    }
+    // the vacated tail: zero, as in an index that never held those rows
+    const RemoveTail t = remove_tail(first_word, kept, N);
+    const size_t Dp = (size_t)ix->Dp;
+    RM_TRY(hipMemsetAsync(ix->X + (size_t)kept * Dp, 0, (size_t)(N - kept) * Dp * sizeof(float), st));
+    RM_TRY(hipMemsetAsync(ix->nrm64 + kept, 0, (size_t)(N - kept) * sizeof(double), st));
+    RM_TRY(hipMemsetAsync(ix->inv32 + kept, 0, (size_t)(N - kept) * sizeof(float), st));
+    RM_TRY(hipMemsetAsync(ix->sq32 + kept, 0, (size_t)(N - kept) * sizeof(float), st));
+    RM_TRY(hipMemsetAsync(ix->rinit32 + kept, 0, (size_t)(N - kept) * sizeof(float), st));
+    // the candidate copies of the moved rows, from the moved rows and the frozen mu / sx / dir.
+    // The tiled copy is rebuilt through its last super tile: X is zero past `kept`, so those
+    // tiles come out zero; whole super tiles past it are zeroed directly.  A copy the current
+    // precision does not read is not rebuilt (set_param rebuilds [0, count) when a setting
+    // starts to read it) but its tail is zeroed all the same.
+    const size_t st_bytes = (size_t)(t.st_end - t.tiles_end) * Dp;  // per byte of an element
+    if (ix->Xs) {
+        if (xs_kind(ix->precision) != kXsNone)
+            RM_TRY(build_candidate_rows(ix, t.rebuild0, t.tiles_end - t.rebuild0, st, true, false));
+        else if (kept % 128)
+            RM_TRY(hipMemsetAsync(reinterpret_cast<char*>(ix->Xs) + (size_t)(kept / 128 * 128) * Dp * 4, 0,
+                                  (size_t)128 * Dp * 4, st));
+        if (st_bytes) RM_TRY(hipMemsetAsync(reinterpret_cast<char*>(ix->Xs) + (size_t)t.tiles_end * Dp * 4, 0, st_bytes * 4, st));
+    }
+    if (ix->Xq) {
+        RM_TRY(launch_zero_rows8(ix->Xq, kept, t.rowz_end - kept, ix->G / 4, st));
+        if (st_bytes) RM_TRY(hipMemsetAsync(reinterpret_cast<char*>(ix->Xq) + (size_t)t.tiles_end * Dp * 2, 0, st_bytes * 2, st));
+        if (ix->Xh) RM_TRY(hipMemsetAsync(ix->Xh + (size_t)kept * Dp, 0, (size_t)(N - kept) * Dp, st));
+        if (needs_i8(ix->precision, ix->auto_i8)) {
+            // the column sums start again: rows below the rebuilt range here, the rest as the
+            // rebuild adds them (exact integers: they equal the sums over [0, kept))
+            RM_TRY(hipMemsetAsync(ix->d_csum, 0, (size_t)2 * Dp * sizeof(uint32_t), st));
+            RM_TRY(launch_colsum8(ix->Xq, 0, t.rebuild0, ix->G / 4, ix->d_csum, st));
+            if (kept > t.rebuild0) RM_TRY(build_candidate_rows(ix, t.rebuild0, kept - t.rebuild0, st, false, true));
+        }
+    }
+    RM_TRY(hipStreamSynchronize(st));
+#undef RM_TRY
+    (void)done(VDB_OK);
+    ix->count = kept;
+    ix->gen++;
+    ix->n_rows_removed += N - kept;
+    ix->auto_hold = 0;  // the rows changed: VDB_PREC_AUTO tries the one-plane passes again
+    ix->auto_fails = 0;
+    ix->auto_hold8 = 0;
+    ix->auto_fails8 = 0;
+    if (ix->h_totals) ix->auto_seen = ix->h_totals[0];
+    if (n_removed) *n_removed = N - kept;
     return VDB_OK;
 }
 
@@ -2120,6 +2276,7 @@ struct vdb_graph {
     int R = 0;
     int knn = 0;                 // kNN candidates per row of the build (vdb_graph_add reuses it)
     int64_t n = 0;
+    int64_t gen = 0;             // the index's generation at build / import / add (rows removed since: stale)
     int64_t cap = 0;             // rows the device neighbour array holds
     int n_entries = 0;
     int32_t* nbr = nullptr;      // device [cap][R]
@@ -2144,6 +2301,7 @@ int graph_upload(vdb_index* ix, int R, int64_t n, const int32_t* nbr_host, const
     g->R = R;
     g->knn = R;
     g->n = n;
+    g->gen = ix->gen.load();
     g->cap = std::max<int64_t>(n, 1);
     g->n_entries = n_ent;
     hipError_t e = hipMalloc(&g->nbr, (size_t)g->cap * R * sizeof(int32_t));
@@ -2341,6 +2499,8 @@ int32_t vdb_graph_add(vdb_graph* g) {
     vdb_index* ix = g->ix;
     HIP_TRY(hipSetDevice(ix->device));
     const int64_t n0 = g->n, N = ix->count;
+    if (g->gen != ix->gen.load())
+        return set_error(VDB_ERR_INVALID, "graph is stale: rows were removed from the index since it was built");
     if (N < n0) return set_error(VDB_ERR_INVALID, "index has fewer rows (%lld) than the graph (%lld)", (long long)N,
                                  (long long)n0);
     if (N == n0) return VDB_OK;
@@ -2481,6 +2641,8 @@ int32_t vdb_graph_search(vdb_graph* g, const float* queries, int32_t nq, int32_t
     std::shared_lock<std::shared_mutex> lk(ix->mu);
     if (ix->count != g->n) return set_error(VDB_ERR_INVALID, "graph is stale: %lld rows, index %lld", (long long)g->n,
                                             (long long)ix->count);
+    if (ix->gen.load() != g->gen)
+        return set_error(VDB_ERR_INVALID, "graph is stale: rows were removed from the index since it was built");
     // device memory: the caller's stream, NULL = the null stream (ordered with the caller's
     // default-stream work, e.g. PyTorch's); host memory: NULL = the index's own stream
     hipStream_t st = (stream || mem == VDB_MEM_DEVICE) ? (hipStream_t)stream : ix->stream;

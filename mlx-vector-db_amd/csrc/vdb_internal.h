@@ -112,6 +112,29 @@ hipError_t launch_split_rows(const float* X, int G, int64_t row0, int64_t n, con
 // Row-major fp32 rows -> fp32 tiles (the PREC_FP32 candidate copy), whole row tiles.
 hipError_t launch_tile_rows(const float* X, int G, int64_t row0, int64_t n, float* Xt, hipStream_t st);
 
+// Row removal (vdb_compact.hip, vdb_index_remove).  The keep-count scan over the remove bitmap
+// (n_words = ceil(count / 32) words, bit r of word r / 32 = row r removed; bits at or past count
+// ignored), three launches: base [n_words + 1] = kept rows below each word (base[n_words] = the
+// total), part [ceil(n_words / 1024)] the per-workgroup partials, info[0] = the total, info[1] =
+// the first word with a removed row (0xFFFFFFFF: none).  remove_scan_bytes: room for all three.
+size_t remove_scan_bytes(int64_t n_words);
+hipError_t launch_remove_scan(const uint32_t* mask, int64_t n_words, int64_t count, uint32_t* base, uint32_t* part,
+                              uint32_t* info, hipStream_t st);
+// One chunk of the gather: the kept rows of source words [w0, w1) (row-major rows of Dp floats and
+// the four per-row scalars) into the scratch, in order, then the scratch to rows
+// [base[w0], base[w1]) of the same arrays.  The scratch holds 32 (w1 - w0) rows.  Chunks run in
+// ascending order on one stream: a chunk's destination ends at or before its source does.
+struct RemoveRows {
+    float* X; int Dp; double* nrm64; float* inv32; float* sq32; float* rinit32;
+};
+struct RemoveScratch {
+    float* X; double* nrm64; float* inv32; float* sq32; float* rinit32;
+};
+hipError_t launch_remove_chunk(const RemoveRows& a, const uint32_t* mask, const uint32_t* base, int64_t count,
+                               int64_t w0, int64_t w1, const RemoveScratch& s, hipStream_t st);
+// both planes of rows [row0, row0 + n) of the int8 copy := 0
+hipError_t launch_zero_rows8(float* Xq, int64_t row0, int64_t n, int G8, hipStream_t st);
+
 // The index's rows -> row-major fp32 [n][D] (export for persistence).
 hipError_t launch_unpack_rows(const float* X, int G, int D, int64_t row0, int64_t n, float* dst, hipStream_t st);
 

@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = (
     "vdb_last_error", "vdb_version", "vdb_device_count",
     "vdb_index_create", "vdb_index_destroy", "vdb_index_reserve",
     "vdb_index_set_param", "vdb_index_get_stat",
-    "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_get_vectors",
+    "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_get_vectors",
     "vdb_index_search", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
@@ -96,6 +96,7 @@ def load_library():
             "vdb_index_add": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
             "vdb_index_count": (c_i32, [c_vp, p_i64]),
             "vdb_index_clear": (c_i32, [c_vp]),
+            "vdb_index_remove": (c_i32, [c_vp, c_vp, c_i32, c_vp, p_i64]),
             "vdb_index_get_vectors": (c_i32, [c_vp, c_i64, c_i64, c_vp]),
             "vdb_index_search": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
@@ -151,6 +152,27 @@ def device_count() -> int:
 
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
+
+
+def rows_to_bitmap(mask_or_rows, count: int) -> np.ndarray:
+    """The uint32 bitmap over ``count`` rows (bit r of word r/32 = row r) that
+    vdb_index_remove takes, from a uint32 bitmap (checked for length) or from an integer array
+    of row ids (ValueError when one is outside [0, count))."""
+    a = np.asarray(mask_or_rows)
+    need = (int(count) + 31) // 32
+    if a.dtype == np.uint32:
+        m = np.ascontiguousarray(a).reshape(-1)
+        if m.size < need:
+            raise ValueError(f"remove mask needs {need} uint32 words, got {m.size}")
+        return m if m.size else np.zeros(1, np.uint32)
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"row ids must be integers (or a uint32 bitmap), got dtype {a.dtype}")
+    rows = a.astype(np.int64, copy=False).reshape(-1)
+    if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= count):
+        raise ValueError(f"row ids must be in [0, {count}), got [{int(rows.min())}, {int(rows.max())}]")
+    bits = np.zeros(max(need, 1) * 32, np.uint8)
+    bits[rows] = 1
+    return np.packbits(bits, bitorder="little").view(np.uint32)
 
 
 class NativeIndex:
@@ -221,6 +243,23 @@ class NativeIndex:
 
     def clear(self) -> None:
         _check(self._lib.vdb_index_clear(self._h))
+
+    def remove(self, mask_or_rows) -> int:
+        """include/vdb.h vdb_index_remove: drop rows, the survivors keep their order and move
+        down.  ``mask_or_rows``: a uint32 bitmap (ceil(count/32) words, bit r of word r/32 = row
+        r removed) or an integer array of row ids (any order, repeats allowed).  Returns the
+        number of rows removed.  An id outside [0, count) raises ValueError and changes nothing."""
+        mask = rows_to_bitmap(mask_or_rows, self.count())
+        n = ctypes.c_int64(0)
+        _check(self._lib.vdb_index_remove(self._h, _ptr(mask), MEM_HOST, None, ctypes.byref(n)))
+        return int(n.value)
+
+    def remove_device(self, mask_ptr: int, stream: int = 0) -> int:
+        """vdb_index_remove with a device-memory bitmap, read after the work queued on ``stream``."""
+        n = ctypes.c_int64(0)
+        _check(self._lib.vdb_index_remove(self._h, ctypes.c_void_p(mask_ptr or None), MEM_DEVICE,
+                                          ctypes.c_void_p(stream or None), ctypes.byref(n)))
+        return int(n.value)
 
     def get_vectors(self, start: int = 0, n: Optional[int] = None) -> np.ndarray:
         total = self.count()

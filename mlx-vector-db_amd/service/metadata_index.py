@@ -80,6 +80,40 @@ class MetadataIndex:
             self._n = r
             self._cache.clear()
 
+    def remove(self, rows) -> int:
+        """Drop the given rows (ids in [0, len), any order, repeats allowed): the survivors keep
+        their order and row r becomes r - (removed rows below r), as the device index renumbers
+        them (include/vdb.h vdb_index_remove).  The postings are renumbered in place of a
+        rebuild, O(total postings); every cached bitmap is dropped.  Returns the rows removed
+        (called under the store's write lock)."""
+        with self._lock:
+            n = self._n
+            ids = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
+            if ids.size and (ids[0] < 0 or ids[-1] >= n):
+                raise ValueError(f"row ids must be in [0, {n}), got [{int(ids[0])}, {int(ids[-1])}]")
+            self._cache.clear()
+            if ids.size == 0:
+                return 0
+            gone = np.zeros(n, bool)
+            gone[ids] = True
+            below = np.cumsum(gone) - gone  # removed rows below each row
+            for key in list(self._post):
+                by_val = self._post[key]
+                for val in list(by_val):
+                    a = np.frombuffer(by_val[val], dtype=np.int64)
+                    a = a[~gone[a]]
+                    if a.size:
+                        lst = array("q")
+                        lst.frombytes((a - below[a]).astype(np.int64).tobytes())
+                        by_val[val] = lst
+                    else:
+                        del by_val[val]
+                if not by_val:
+                    del self._post[key]
+            self._rows = [m for m, g in zip(self._rows, gone.tolist()) if not g]
+            self._n = n - int(ids.size)
+            return int(ids.size)
+
     def _pair_rows(self, key: Any, value: Any, n: int) -> np.ndarray:
         """Sorted rows < n with ``meta.get(key) == value``."""
         # rows past the metadata list (the reference allows fewer metadata entries than vectors;

@@ -324,6 +324,70 @@ class MLXVectorStore:
                 self._hnsw_index.add_rows(self._index, n0)
             return {"vectors_added": len(metadata), "total_vectors": self._vector_count}
 
+    # ---- delete ----------------------------------------------------------------------
+    def delete_vectors(self, filter_metadata: Optional[Dict]) -> Dict[str, int]:
+        """Delete every row whose metadata matches ``filter_metadata`` (the filter semantics of
+        ``query``).  The reference store cannot delete; its Python SDK expects the capability
+        (sdk/python/mlx_vector_db_client.py:292-303, POST /vectors/delete).  The rows are
+        compacted on the device (include/vdb.h vdb_index_remove); the survivors keep their order
+        and are renumbered.  An empty filter raises: ``clear()`` deletes everything."""
+        self._check_can_delete()
+        if not filter_metadata:
+            raise ValueError("delete_vectors needs a non-empty filter_metadata; use clear() to delete everything")
+        with self._lock, _Write(self._rw):
+            n = self._vector_count
+            if n == 0:
+                return {"deleted": 0, "total_vectors": 0}
+            mask, hits = self._meta_index.bitmap(filter_metadata, n)
+            if hits == 0:
+                return {"deleted": 0, "total_vectors": n}
+            return self._delete_locked(mask)
+
+    def delete_rows(self, indices) -> Dict[str, int]:
+        """``delete_vectors`` by position: row ids in [0, count), any order."""
+        self._check_can_delete()
+        with self._lock, _Write(self._rw):
+            n = self._vector_count
+            ids = np.asarray(indices).reshape(-1)
+            if ids.size == 0:
+                return {"deleted": 0, "total_vectors": n}
+            if ids.dtype.kind not in "iu":
+                raise ValueError(f"row ids must be integers, got dtype {ids.dtype}")
+            return self._delete_locked(_vdb.rows_to_bitmap(ids.astype(np.int64), n))
+
+    def _check_can_delete(self):
+        if len(self._devices()) > 1:
+            raise NotImplementedError("delete is not supported on a multi-device store")
+
+    def _delete_locked(self, mask: np.ndarray) -> Dict[str, int]:
+        """Remove the rows of a uint32 bitmap over [0, count) (write locks held)."""
+        n = self._vector_count
+        rows = np.nonzero(np.unpackbits(np.ascontiguousarray(mask, np.uint32).view(np.uint8),
+                                        bitorder="little")[:n])[0]
+        deleted = self._index.remove(mask)
+        gone = set(rows.tolist())
+        self._metadata = [m for i, m in enumerate(self._metadata) if i not in gone]
+        self._meta_index.remove(rows[rows < len(self._meta_index)])
+        self._vector_count = self._index.count()
+        if self.config.persist:
+            # the reference's cost model, a full rewrite per mutation (:113, :218-223): the base
+            # files hold the survivors at once and the append log is dropped
+            if self._vector_count:
+                self._is_dirty = True
+                self._save_store(force=True)
+            else:
+                self._files.remove_all()
+                self._is_dirty = False
+        else:
+            self._is_dirty = True
+        if self.config.enable_hnsw and self._hnsw_index is not None:
+            # a graph over the old numbering is stale for good: rebuilt from the index, as the
+            # reference rebuilds on every add (:110-112)
+            # (an emptied store answers no query; the next add rebuilds: add_rows sees the old count)
+            if self._vector_count:
+                self._hnsw_index.build(None, native_index=self._index)
+        return {"deleted": int(deleted), "total_vectors": self._vector_count}
+
     # ---- query ---------------------------------------------------------------------
     def query(self, query_vector: Union[np.ndarray, Any], k: int = 10,
               filter_metadata: Optional[Dict] = None, use_hnsw: bool = True) -> Tuple:

@@ -166,6 +166,18 @@ class StoreFiles:
         self._remove_log()
         self.log_rows = 0
 
+    def remove_all(self) -> None:
+        """The store lost its last row (a delete): no base files, no log.  The log goes first,
+        so a stop in between leaves the (older, longer) base alone, never a log without one."""
+        self._remove_log()
+        for name in (BASE_VECTORS, BASE_META):
+            try:
+                (self.path / name).unlink()
+            except FileNotFoundError:
+                pass
+        self.base_rows = 0
+        self.log_rows = 0
+
     # ---- helpers ----------------------------------------------------------------
     def _read_info(self):
         p = self.path / LOG_INFO
