@@ -145,12 +145,14 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "scan_checksum" (1 default, 0 off, 2 also I8X3's L sums), "pilot_tiles", "pilot_rank",
  * "finish_split", "finish_small" (-1 auto: the finish's 4-wave form beside a long-row
  * wide scan for batches of >= 32, 0 off, 1 on), "i8_refine", "i8_narrow", "device_repass", "auto_int8", "auto_i8q",
- * "dir_bound" (0: BF16 certificate with |q| R only).  Stats also: "searches", "queries",
+ * "dir_bound" (0: BF16 certificate with |q| R only), "remove_chunk" / "update_chunk" (rows per
+ * chunk of vdb_index_remove's scratch / vdb_index_update's staging, 0 = by bytes).  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
  * each; with VDB_PREC_AUTO these show its choices), "searches_q4", "searches_wide",
- * "auto_int8", "i8q_off", "i8_wide", "split_copy", "split_copy_builds". */
+ * "auto_int8", "i8q_off", "i8_wide", "split_copy", "split_copy_builds", "rows_removed",
+ * "rows_updated". */
 int32_t vdb_index_set_param(vdb_index* idx, const char* name, int64_t value);
 int32_t vdb_index_get_stat(const vdb_index* idx, const char* name, int64_t* value);
 
@@ -183,6 +185,31 @@ int32_t vdb_index_clear(vdb_index* idx);
  * once later adds bring the count back. */
 int32_t vdb_index_remove(vdb_index* idx, const uint32_t* remove_mask, int32_t mem, void* stream,
                          int64_t* n_removed);
+/* Update rows in place: row rows[i] becomes vectors[i] (i < n; vectors [n][dim] row-major fp32,
+ * rows n ids in [0, count), pairwise distinct, any order).  mem: VDB_MEM_HOST or VDB_MEM_DEVICE,
+ * both pointers of the same kind; device-memory arguments are read after the work queued on
+ * `stream` (NULL = the null stream).  Returns when done; count and capacity stay; n == 0 is
+ * VDB_OK and touches nothing.
+ * Replaces: nothing in the reference's store, which cannot change a vector it holds; the
+ * counterpart is the `upsert` its own benchmark calls on the database it compares itself with
+ * (benchmarks/benchmark_app.py:104).  Without this call: vdb_index_remove + vdb_index_add, which
+ * compacts and renumbers every row above the first removed one.
+ * All or nothing: an id outside [0, count) or a repeated id -> VDB_ERR_INVALID, a NaN or Inf in
+ * vectors -> VDB_ERR_NONFINITE, and the index is exactly as it was (rows, norms, candidate
+ * copies, column sums, running maxima).  An update overwrites live rows, so validation is a pass
+ * of its own before the first write: one kernel per staged chunk checks range, finiteness and
+ * repeats (a ceil(count/32)-word scratch bitmap), the host reads the flags (one sync), then the
+ * apply is queued.  A host-memory call of more than one staging chunk therefore sends its rows
+ * to the device twice, once to validate and once to apply.
+ * The apply rewrites, for the updated rows only, the fp32 row and its row terms, the candidate
+ * copies the current precision reads (the lazily built split copy included) and the int8 copy's
+ * column sums (old bytes out, new bytes in); the centring row, quantisation step and residual
+ * direction stay as they are and the running maxima are only raised (DESIGN.md "Updating rows").
+ * Waits for the searches queued on this index first.  Knob "update_chunk" (rows per staging
+ * chunk, 0 = sized by bytes at 256 MiB as an add's staging); stat "rows_updated" (cumulative).
+ * A graph built before an update is stale (search and add report it). */
+int32_t vdb_index_update(vdb_index* idx, const int64_t* rows, const float* vectors, int64_t n, int32_t mem,
+                         void* stream);
 /* Copy rows [start, start+n) back out, row-major fp32, to host memory (used for
  * vectors.npz persistence, service/optimized_vector_store.py:218-223). */
 int32_t vdb_index_get_vectors(vdb_index* idx, int64_t start, int64_t n, float* out_host);

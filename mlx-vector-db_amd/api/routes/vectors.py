@@ -91,6 +91,20 @@ class VectorDeleteResponse(BaseModel):
     processing_time_ms: float
 
 
+class VectorUpsertRequest(VectorAddRequest):
+    """/vectors/add's body plus the metadata key that names a row.  Rows are addressed by key,
+    not by position: query results expose metadata only."""
+    key: str = Field(default="id", description="Metadata key whose value identifies a row")
+
+
+class VectorUpsertResponse(BaseModel):
+    success: bool
+    updated: int
+    added: int
+    total_vectors: int
+    processing_time_ms: float
+
+
 class VectorAddResponse(BaseModel):
     success: bool
     vectors_added: int
@@ -301,6 +315,25 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:  # as the sibling routes: every error becomes a 500
             logger.error("Error deleting vectors: %s", e)
             raise HTTPException(status_code=500, detail=f"Failed to delete vectors: {e}")
+
+    @router.post("/upsert", response_model=VectorUpsertResponse)
+    async def upsert_vectors(request: VectorUpsertRequest, api_key: str = Depends(auth)):
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if not request.vectors or not request.metadata:
+                raise HTTPException(status_code=400, detail="Vectors and metadata required")
+            import numpy as np
+            vectors_np = np.array(request.vectors, dtype=np.float32)
+            loop = asyncio.get_running_loop()
+            res = await loop.run_in_executor(
+                mgr._executor, lambda: store.upsert_vectors(vectors_np, request.metadata, key=request.key))
+            return VectorUpsertResponse(success=True, updated=res["updated"], added=res["added"],
+                                        total_vectors=res["total_vectors"],
+                                        processing_time_ms=(time.time() - t0) * 1000)
+        except Exception as e:  # as /vectors/add: every error, a store ValueError included, becomes a 500
+            logger.error("Error upserting vectors: %s", e)
+            raise HTTPException(status_code=500, detail=f"Failed to upsert vectors: {e}")
 
     @router.get("/count")
     async def get_vector_count(user_id: str, model_id: str, api_key: str = Depends(auth)):

@@ -213,14 +213,17 @@ struct vdb_index {
     int64_t scan_wide = -1;
     // vdb_index_remove: rows per chunk of the gather's scratch (0 = by bytes, vdb_compact_plan.h)
     int64_t remove_chunk = 0;
-    // bumped whenever rows leave or move (remove, clear): a graph built before is stale even
-    // when a later add brings the count back to what it recorded
+    // vdb_index_update: rows per staging chunk (0 = by bytes, 256 MiB as an add's staging)
+    int64_t update_chunk = 0;
+    // bumped whenever rows leave, move or change (remove, clear, update): a graph built before is
+    // stale even when the count is (again) what it recorded
     std::atomic<int64_t> gen{0};
     // stats
     std::atomic<int64_t> n_searches{0}, n_queries{0}, n_fallback{0}, n_overflow{0}, n_incons{0}, n_repass{0}, n_q4{0};
     std::atomic<int64_t> n_wide{0};  // searches through the wide int8 pass
     std::atomic<int64_t> n_xs_builds{0};  // lazy builds of the split copy (ensure_xs)
     std::atomic<int64_t> n_rows_removed{0};  // rows removed by vdb_index_remove (cumulative)
+    std::atomic<int64_t> n_rows_updated{0};  // rows rewritten by vdb_index_update (cumulative)
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -906,6 +909,10 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
         if (value < 0) return set_error(VDB_ERR_INVALID, "remove_chunk must be >= 0 (0 = sized by bytes)");
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->remove_chunk = value;
+    } else if (n == "update_chunk") {
+        if (value < 0) return set_error(VDB_ERR_INVALID, "update_chunk must be >= 0 (0 = sized by bytes)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->update_chunk = value;
     } else if (n == "device_repass") {
         if (value < -1 || value > 1) return set_error(VDB_ERR_INVALID, "device_repass must be -1, 0 or 1");
         ix->device_repass = value;
@@ -998,6 +1005,7 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     } else if (n == "split_copy") *value = xs_ptr(ix) ? 1 : 0;
     else if (n == "split_copy_builds") *value = ix->n_xs_builds.load();
     else if (n == "rows_removed") *value = ix->n_rows_removed.load();
+    else if (n == "rows_updated") *value = ix->n_rows_updated.load();
     else return set_error(VDB_ERR_INVALID, "unknown stat '%s'", name);
     return VDB_OK;
 }
@@ -1364,6 +1372,138 @@ int32_t vdb_index_remove(vdb_index* ix, const uint32_t* remove_mask, int32_t mem
     ix->auto_fails8 = 0;
     if (ix->h_totals) ix->auto_seen = ix->h_totals[0];
     if (n_removed) *n_removed = N - kept;
+    return VDB_OK;
+}
+
+int32_t vdb_index_update(vdb_index* ix, const int64_t* rows, const float* vectors, int64_t n, int32_t mem,
+                         void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (n < 0) return set_error(VDB_ERR_INVALID, "n must be >= 0");
+    if (n == 0) return VDB_OK;
+    if (!rows || !vectors) return set_error(VDB_ERR_INVALID, "rows or vectors is NULL");
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    if (n > N) return set_error(VDB_ERR_INVALID, "%lld distinct rows of %lld cannot be updated", (long long)n, (long long)N);
+    // queued device-memory searches on caller streams read the rows this call overwrites
+    {
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+    }
+    hipStream_t st = ix->stream;
+    const int D = ix->dim;
+    const int64_t by_bytes = std::max<int64_t>(1, (int64_t)(256ll << 20) / ((int64_t)D * 4));
+    const int64_t chunk = std::min(n, ix->update_chunk > 0 ? ix->update_chunk : by_bytes);
+    const bool host = mem == VDB_MEM_HOST;
+    // one allocation: the repeat bitmap, the flags and (host-memory arguments) one staging chunk
+    // of ids and rows
+    const size_t n_words = (size_t)((N + 31) / 32);
+    const size_t bytes = n_words * sizeof(uint32_t) + 4 * sizeof(uint32_t) +
+                         (host ? (size_t)chunk * ((size_t)D * sizeof(float) + sizeof(int64_t)) : 0) + 4 * 256;
+    char* buf = nullptr;
+    HIP_TRY(hipMalloc(&buf, bytes));
+    auto done = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(buf);
+        return rc;
+    };
+#define UP_TRY(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t _e = (expr);                                                                        \
+        if (_e != hipSuccess)                                                                          \
+            return done(set_error(_e == hipErrorOutOfMemory ? VDB_ERR_OOM : VDB_ERR_HIP, "update: %s failed: %s", \
+                                  #expr, hipGetErrorString(_e)));                                      \
+    } while (0)
+    Carver c{buf};
+    uint32_t* bitmap = c.take<uint32_t>(n_words);
+    uint32_t* flags = c.take<uint32_t>(4);
+    int64_t* s_ids = host ? c.take<int64_t>((size_t)chunk) : nullptr;
+    float* s_rows = host ? c.take<float>((size_t)chunk * D) : nullptr;
+    if (!host) {
+        // the ids and rows may still be being written on the caller's stream (NULL = the null stream)
+        hipEvent_t ready = nullptr;
+        UP_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(ready, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, ready, 0);
+        (void)hipEventDestroy(ready);
+        UP_TRY(e);
+    }
+    // chunk [r, r + m) of the call on the device: staged (host memory; the staging is free again
+    // once the stream has run what read it) or where the caller put it
+    const int64_t* d_ids = nullptr;
+    const float* d_rows = nullptr;
+    auto stage = [&](int64_t r, int64_t m) -> hipError_t {
+        if (!host) {
+            d_ids = rows + r;
+            d_rows = vectors + r * D;
+            return hipSuccess;
+        }
+        hipError_t e = hipMemcpyAsync(s_ids, rows + r, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(s_rows, vectors + r * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice, st);
+        d_ids = s_ids;
+        d_rows = s_rows;
+        return e;
+    };
+    // 1. validation, before the first write: range, repeats, finiteness
+    UP_TRY(hipMemsetAsync(bitmap, 0, n_words * sizeof(uint32_t), st));
+    UP_TRY(hipMemsetAsync(flags, 0, 4 * sizeof(uint32_t), st));
+    for (int64_t r = 0; r < n; r += chunk) {
+        const int64_t m = std::min(chunk, n - r);
+        UP_TRY(stage(r, m));
+        UP_TRY(launch_update_validate(d_ids, d_rows, m, D, N, bitmap, flags, st));
+        if (host && r + m < n) UP_TRY(hipStreamSynchronize(st));  // staging reuse
+    }
+    uint32_t h_flags[4] = {0, 0, 0, 0};
+    UP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, st));
+    UP_TRY(hipStreamSynchronize(st));
+    if (h_flags[0])
+        return done(set_error(VDB_ERR_INVALID, "update: a row id is outside [0, %lld); nothing was updated", (long long)N));
+    if (h_flags[1]) return done(set_error(VDB_ERR_INVALID, "update: a row id is given more than once; nothing was updated"));
+    if (h_flags[2])
+        return done(set_error(VDB_ERR_NONFINITE, "%u row(s) contain NaN or Inf; nothing was updated", h_flags[2]));
+    // 2. the apply, for the updated rows only, with mu / sx / dir as they are
+    const float* inv = ix->metric == VDB_METRIC_COSINE ? ix->inv32 : nullptr;
+    const bool i8 = ix->Xq && needs_i8(ix->precision, ix->auto_i8);
+    const int kind = ix->Xs ? xs_kind(ix->precision) : kXsNone;
+    const int G8 = ix->G / 4;
+    UP_TRY(hipMemsetAsync(ix->d_nonfinite, 0, sizeof(int), st));
+    for (int64_t r = 0; r < n; r += chunk) {
+        const int64_t m = std::min(chunk, n - r);
+        if (n > chunk || !host) UP_TRY(stage(r, m));  // (a single host chunk is still staged)
+        // the old bytes leave the column sums before they are overwritten
+        if (i8) UP_TRY(launch_update_colsum8(ix->Xq, d_ids, m, N, G8, -1, ix->d_csum, st));
+        UP_TRY(launch_update_pack_rows(d_rows, d_ids, m, N, D, ix->G, ix->X, ix->nrm64, ix->inv32, ix->sq32,
+                                       ix->rinit32, ix->metric == VDB_METRIC_COSINE, ix->d_xmax, ix->d_nonfinite, st));
+        if (kind == kXsFp32) UP_TRY(launch_update_tile_rows(ix->X, ix->G, d_ids, m, N, ix->Xs, st));
+        if (kind == kXsSplit) UP_TRY(launch_update_split_rows(ix->X, ix->G, d_ids, m, N, inv, ix->Xs, st));
+        if (i8) {
+            UP_TRY(launch_update_quant_rows(ix->X, inv, ix->d_mu, ix->d_dir, ix->sx, d_ids, m, N, ix->G, ix->Xq,
+                                            ix->d_i8, ix->Xh, st));
+            UP_TRY(launch_update_colsum8(ix->Xq, d_ids, m, N, G8, +1, ix->d_csum, st));
+        }
+        UP_TRY(launch_update_resid_dir(ix->X, inv, d_ids, m, N, D, ix->G, ix->d_dir, ix->d_xmax + 3, st));
+        if (host && r + m < n) UP_TRY(hipStreamSynchronize(st));  // staging reuse
+    }
+    unsigned long long xb[4] = {0, 0, 0, 0};
+    UP_TRY(hipMemcpyAsync(xb, ix->d_xmax, sizeof(xb), hipMemcpyDeviceToHost, st));
+    UP_TRY(read_i8_stats(ix, st));  // (synchronises)
+#undef UP_TRY
+    (void)done(VDB_OK);
+    double xm[4];
+    std::memcpy(xm, xb, sizeof(xm));
+    ix->xmax = xm[0];
+    ix->xres_rel = xm[1];
+    ix->xres_abs = xm[2];
+    ix->xres_dir = xm[3];
+    ix->gen++;
+    ix->n_rows_updated += n;
+    ix->auto_hold = 0;  // the rows changed: VDB_PREC_AUTO tries the one-plane passes again
+    ix->auto_fails = 0;
+    ix->auto_hold8 = 0;
+    ix->auto_fails8 = 0;
+    if (ix->h_totals) ix->auto_seen = ix->h_totals[0];
     return VDB_OK;
 }
 
@@ -2500,7 +2640,7 @@ int32_t vdb_graph_add(vdb_graph* g) {
     HIP_TRY(hipSetDevice(ix->device));
     const int64_t n0 = g->n, N = ix->count;
     if (g->gen != ix->gen.load())
-        return set_error(VDB_ERR_INVALID, "graph is stale: rows were removed from the index since it was built");
+        return set_error(VDB_ERR_INVALID, "graph is stale: rows were removed from or updated in the index since it was built");
     if (N < n0) return set_error(VDB_ERR_INVALID, "index has fewer rows (%lld) than the graph (%lld)", (long long)N,
                                  (long long)n0);
     if (N == n0) return VDB_OK;
@@ -2642,7 +2782,7 @@ int32_t vdb_graph_search(vdb_graph* g, const float* queries, int32_t nq, int32_t
     if (ix->count != g->n) return set_error(VDB_ERR_INVALID, "graph is stale: %lld rows, index %lld", (long long)g->n,
                                             (long long)ix->count);
     if (ix->gen.load() != g->gen)
-        return set_error(VDB_ERR_INVALID, "graph is stale: rows were removed from the index since it was built");
+        return set_error(VDB_ERR_INVALID, "graph is stale: rows were removed from or updated in the index since it was built");
     // device memory: the caller's stream, NULL = the null stream (ordered with the caller's
     // default-stream work, e.g. PyTorch's); host memory: NULL = the index's own stream
     hipStream_t st = (stream || mem == VDB_MEM_DEVICE) ? (hipStream_t)stream : ix->stream;

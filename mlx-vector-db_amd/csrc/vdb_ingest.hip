@@ -2,6 +2,7 @@
 // (pipeline overview: vdb_scan.hip).  Built with -ffp-contract=off.
 #include "vdb_common.h"
 #include "vdb_internal.h"
+#include "vdb_row_ops.h"
 
 namespace vdb {
 
@@ -22,64 +23,8 @@ __global__ void __launch_bounds__(256) pack_rows_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
-    const int Dp = G * GROUP_DIMS;
-    const int np = (D + 255) / 256;
-    const float* s = src + row * (int64_t)D;
-    const uint64_t r = (uint64_t)(row0 + row);
-    double acc = 0.0;
-    int bad = 0;
-    for (int m = 0; m < np; ++m) {
-        const int p = m * 64 + lane;
-        f32x4 v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int d = 4 * p + j;
-            v[j] = d < D ? s[d] : 0.0f;
-            bad |= !isfinite(v[j]);
-            const double dv = (double)v[j];
-            acc = acc + dv * dv;
-        }
-        if (4 * p < Dp) *(f32x4*)(X + row_piece_offset(r, p, G)) = v;
-    }
-    acc = wave_sum_butterfly(acc);
-    const double nr = sqrt(acc);
-    const float iv = (float)(1.0 / fmax(nr, 1e-8));
-    // the split copy's row and its bf16 residual |y - bf16(y)|
-    double res = 0.0, yy = 0.0;
-    for (int m = 0; m < np; ++m) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int d = 4 * (m * 64 + lane) + j;
-            const float x = d < D ? s[d] : 0.0f;
-            const float y = normalise ? x * iv : x;
-            const double rv = (double)y - (double)__uint_as_float(bf16_rne_bits(y) << 16);
-            res = res + rv * rv;
-            yy = yy + (double)y * (double)y;
-        }
-    }
-    res = wave_sum_butterfly(res);
-    yy = wave_sum_butterfly(yy);
-    const int anybad = __any(bad);
-    if (lane == 0) {
-        nrm64[r] = nr;
-        inv32[r] = iv;
-        sq32[r] = (float)acc;
-        rinit32[r] = -0.5f * (float)acc;
-        if (anybad) {
-            atomicAdd(nonfinite, 1);
-        } else {
-            // xmax_bits[0] max |x|; [1] max |y - bf16(y)| / max(|y|, 1e-8); [2] max |y - bf16(y)|
-            // (non-negative doubles order like their bit patterns; a plain read first: the
-            // maxima are monotone, so a stale value only lets an atomic through)
-            const double dr = sqrt(res);
-            const unsigned long long v[3] = {(unsigned long long)__double_as_longlong(nr),
-                                             (unsigned long long)__double_as_longlong(dr / fmax(sqrt(yy), 1e-8)),
-                                             (unsigned long long)__double_as_longlong(dr)};
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                if (v[i] > __atomic_load_n(xmax_bits + i, __ATOMIC_RELAXED)) atomicMax(xmax_bits + i, v[i]);
-        }
-    }
+    pack_row(src + row * (int64_t)D, (uint64_t)(row0 + row), lane, D, G, X, nrm64, inv32, sq32, rinit32, normalise,
+             xmax_bits, nonfinite);
 }
 
 hipError_t launch_pack_rows(const float* src, int64_t n, int D, int G, float* X, int64_t row0, double* nrm64,
@@ -130,27 +75,7 @@ __global__ void __launch_bounds__(256) resid_dir_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
-    const uint64_t r = (uint64_t)(row0 + i);
-    const float iv = inv32 ? inv32[r] : 1.0f;
-    const int np = (D + 255) / 256;
-    double acc = 0.0;
-    for (int m = 0; m < np; ++m) {
-        const int p = m * 64 + lane;
-        if (4 * p >= D) break;
-        const f32x4 xv = *(const f32x4*)(X + row_piece_offset(r, p, G));
-        const f32x4 dv = *(const f32x4*)(dir + 4 * p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float y = inv32 ? xv[j] * iv : xv[j];
-            const double rv = (double)y - (double)__uint_as_float(bf16_rne_bits(y) << 16);
-            acc = acc + (double)dv[j] * rv;
-        }
-    }
-    acc = wave_sum_butterfly(acc);
-    if (lane == 0) {
-        const unsigned long long v = (unsigned long long)__double_as_longlong(fabs(acc));
-        if (v > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, v);
-    }
+    resid_dir_row(X, inv32, (uint64_t)(row0 + i), lane, D, G, dir, out);
 }
 
 hipError_t launch_resid_dir(const float* X, const float* inv32, int64_t row0, int64_t n, int D, int G,
@@ -174,19 +99,7 @@ __global__ void __launch_bounds__(256) split_rows_kernel(const float* __restrict
     const int i = (int)(idx & 31);
     const int g8 = (int)((idx >> 5) % G);
     const uint64_t t = (uint64_t)(t0 + (idx >> 5) / G);
-    const float* src = X + row_piece_offset(t * 32 + i, 2 * g8, G);
-    f32x4 a = *(const f32x4*)src;
-    f32x4 b = *(const f32x4*)(src + 4);
-    if (inv32) {
-        const float iv = inv32[t * 32 + i];
-        a *= iv;
-        b *= iv;
-    }
-    f32x4 hi, lo;
-    split8(a, b, hi, lo);
-    float* dst = Xs + corpus_block(t, g8 >> 1, 0, G >> 1) + (size_t)(i + 32 * (g8 & 1)) * 4;
-    *(f32x4*)dst = hi;
-    *(f32x4*)(dst + corpus_plane(G >> 1)) = lo;
+    split_row_piece(X, G, t * 32 + i, g8, inv32, Xs);
 }
 
 hipError_t launch_split_rows(const float* X, int G, int64_t row0, int64_t n, const float* inv32, float* Xs,
@@ -208,7 +121,7 @@ __global__ void __launch_bounds__(256) tile_rows_kernel(const float* __restrict_
     const int i = (int)(idx & 31);
     const int p = (int)((idx >> 5) % (2 * G));
     const uint64_t r = (uint64_t)(t0 + (idx >> 5) / (2 * G)) * 32 + i;
-    *(f32x4*)(Xt + tiled_piece_offset(r, p, G)) = *(const f32x4*)(X + row_piece_offset(r, p, G));
+    tile_row_piece(X, G, r, p, Xt);
 }
 
 hipError_t launch_tile_rows(const float* X, int G, int64_t row0, int64_t n, float* Xt, hipStream_t st) {

@@ -135,6 +135,31 @@ hipError_t launch_remove_chunk(const RemoveRows& a, const uint32_t* mask, const 
 // both planes of rows [row0, row0 + n) of the int8 copy := 0
 hipError_t launch_zero_rows8(float* Xq, int64_t row0, int64_t n, int G8, hipStream_t st);
 
+// In-place row update (vdb_update.hip, vdb_index_update).  Validation of one staged chunk: ids [n]
+// and rows src [n][D]; flags[0] |= 1 for an id outside [0, count), flags[1] |= 1 for an id seen
+// before in this call (bitmap: ceil(count / 32) words, zeroed before the first chunk), flags[2] +=
+// the rows holding a NaN or Inf.  Nothing of the index is read or written.
+hipError_t launch_update_validate(const int64_t* ids, const float* src, int64_t n, int D, int64_t count,
+                                  uint32_t* bitmap, uint32_t* flags, hipStream_t st);
+// The ingest launchers above over the rows ids[0 .. n) (pairwise distinct, in [0, count); an id
+// outside is skipped) instead of [row0, row0 + n): the same per-row arithmetic (vdb_row_ops.h).
+// pack: row ids[i] := src[i].
+hipError_t launch_update_pack_rows(const float* src, const int64_t* ids, int64_t n, int64_t count, int D, int G,
+                                   float* X, double* nrm64, float* inv32, float* sq32, float* rinit32, int normalise,
+                                   unsigned long long* xmax_bits, int* nonfinite, hipStream_t st);
+hipError_t launch_update_resid_dir(const float* X, const float* inv32, const int64_t* ids, int64_t n, int64_t count,
+                                   int D, int G, const float* dir, unsigned long long* out, hipStream_t st);
+hipError_t launch_update_split_rows(const float* X, int G, const int64_t* ids, int64_t n, int64_t count,
+                                    const float* inv32, float* Xs, hipStream_t st);
+hipError_t launch_update_tile_rows(const float* X, int G, const int64_t* ids, int64_t n, int64_t count, float* Xt,
+                                   hipStream_t st);
+hipError_t launch_update_quant_rows(const float* X, const float* inv32, const float* mu, const float* dir, float sx,
+                                    const int64_t* ids, int64_t n, int64_t count, int G, float* Xq,
+                                    unsigned long long* stats, int8_t* xh_rm, hipStream_t st);
+// csum [2][Dp] += sign * (column sums of the int8 copy's planes over the listed rows), mod 2^32
+hipError_t launch_update_colsum8(const float* Xq, const int64_t* ids, int64_t n, int64_t count, int G8, int sign,
+                                 uint32_t* csum, hipStream_t st);
+
 // The index's rows -> row-major fp32 [n][D] (export for persistence).
 hipError_t launch_unpack_rows(const float* X, int G, int D, int64_t row0, int64_t n, float* dst, hipStream_t st);
 

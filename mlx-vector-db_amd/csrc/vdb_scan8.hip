@@ -2,6 +2,7 @@
 // the corpus quantisation at ingest, the per-batch query quantisation, the pilot with the same
 // arithmetic, and the dispatch to the instantiation units.
 #include "vdb_scan8_kernel.h"
+#include "vdb_row_ops.h"
 
 // scan_qlds auto (-1): the query block in LDS for short rows (rule 1) and, past 768 dims,
 // whenever it fits (rule 2).  Measured (profiles/r04_qlds, same box): C3 (D = 1536) scan 0.625
@@ -46,25 +47,6 @@ hipError_t launch_zmax(const float* X, const float* inv32, const float* mu, int6
     return hipGetLastError();
 }
 
-// 16 values -> 16 int8 (byte j = element j) in one f32x4
-__device__ __forceinline__ f32x4 pack_i8x16(const int (&v)[16]) {
-    f32x4 o;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const uint32_t u = (uint32_t)(v[4 * w] & 255) | ((uint32_t)(v[4 * w + 1] & 255) << 8) |
-                           ((uint32_t)(v[4 * w + 2] & 255) << 16) | ((uint32_t)(v[4 * w + 3] & 255) << 24);
-        o[w] = __uint_as_float(u);
-    }
-    return o;
-}
-
-// t -> (hi, lo) with t ~ hi + lo / 256, |hi|, |lo| <= 127 (values past the range clip; the
-// residual the statistics measure then shows it)
-__device__ __forceinline__ void split_i8(float t, int& hi, int& lo) {
-    hi = (int)fminf(fmaxf(rintf(t), -127.0f), 127.0f);
-    lo = (int)fminf(fmaxf(rintf((t - (float)hi) * 256.0f), -127.0f), 127.0f);
-}
-
 // One wave per row: z = y - mu, xh / xl planes of the int8 copy (block (tile, 32-dim group g,
 // plane) lane i + 32 h holds dims 32 g + 16 h .. + 15 of row 32 t + i), and the row statistics
 // (fp64 bits, running maxima) stats[0] |z - s_x xh|, [1] |dir.(z - s_x xh)|, [2] |z - z~|,
@@ -77,66 +59,7 @@ __global__ void __launch_bounds__(256) quant_rows_kernel(const float* __restrict
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
-    const uint64_t r = (uint64_t)(row0 + i);
-    const float iv = inv32 ? inv32[r] : 1.0f;
-    const float isx = 1.0f / sx;
-    const int G8 = G >> 2;
-    const int nc = 2 * G8;  // 16-dim chunks
-    double s_r8 = 0.0, s_d8 = 0.0, s_r16 = 0.0, s_d16 = 0.0, s_h = 0.0, s_l = 0.0;
-    for (int c = lane; c < nc; c += 64) {
-        const float* src = X + (size_t)r * (size_t)(8 * G) + 16 * c;
-        int hv[16], lv[16];
-#pragma unroll
-        for (int j4 = 0; j4 < 4; ++j4) {
-            const f32x4 xv = *(const f32x4*)(src + 4 * j4);
-            const f32x4 mv = *(const f32x4*)(mu + 16 * c + 4 * j4);
-            const f32x4 dv = *(const f32x4*)(dir + 16 * c + 4 * j4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float z = (inv32 ? xv[j] * iv : xv[j]) - mv[j];
-                int h, l;
-                split_i8(z * isx, h, l);
-                hv[4 * j4 + j] = h;
-                lv[4 * j4 + j] = l;
-                const double zh = (double)sx * h, zl = (double)sx * l / 256.0;
-                const double r8 = (double)z - zh, r16 = r8 - zl;
-                s_r8 += r8 * r8;
-                s_r16 += r16 * r16;
-                s_d8 += (double)dv[j] * r8;
-                s_d16 += (double)dv[j] * r16;
-                s_h += zh * zh;
-                s_l += zl * zl;
-            }
-        }
-        const uint64_t t = r >> 5;
-        float* dst = Xq + corpus_block(t, c >> 1, 0, G8) + (size_t)((r & 31) + 32 * (c & 1)) * 4;
-        *(f32x4*)dst = pack_i8x16(hv);
-        *(f32x4*)(dst + corpus_plane(G8)) = pack_i8x16(lv);
-        // the xh plane row-major too (as xh + 128): the finish's refinement reads candidates' rows whole
-        if (xh_rm) {  // biased to unsigned (xh + 128): one v_cvt_f32_ubyte per element in the finish
-            int uv[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) uv[j] = hv[j] + 128;
-            *(f32x4*)(xh_rm + r * (size_t)(8 * G) + 16 * c) = pack_i8x16(uv);
-        }
-    }
-    s_r8 = wave_sum_butterfly(s_r8);
-    s_d8 = wave_sum_butterfly(s_d8);
-    s_r16 = wave_sum_butterfly(s_r16);
-    s_d16 = wave_sum_butterfly(s_d16);
-    s_h = wave_sum_butterfly(s_h);
-    s_l = wave_sum_butterfly(s_l);
-    if (lane == 0) {
-        const double v[6] = {sqrt(s_r8), fabs(s_d8), sqrt(s_r16), fabs(s_d16), sqrt(s_h), sqrt(s_l)};
-        bool fin = true;  // a non-finite row (the whole add is rejected) leaves no statistics
-#pragma unroll
-        for (int k = 0; k < 6; ++k) fin = fin && isfinite(v[k]);
-#pragma unroll
-        for (int k = 0; k < 6 && fin; ++k) {
-            const unsigned long long b = (unsigned long long)__double_as_longlong(v[k]);
-            if (b > __atomic_load_n(stats + k, __ATOMIC_RELAXED)) atomicMax(stats + k, b);
-        }
-    }
+    quant_row(X, inv32, mu, dir, sx, (uint64_t)(row0 + i), lane, G, Xq, stats, xh_rm);
 }
 
 hipError_t launch_quant_rows(const float* X, const float* inv32, const float* mu, const float* dir, float sx,

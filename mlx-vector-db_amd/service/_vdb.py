@@ -39,7 +39,8 @@ EXPORTED_SYMBOLS = (
     "vdb_last_error", "vdb_version", "vdb_device_count",
     "vdb_index_create", "vdb_index_destroy", "vdb_index_reserve",
     "vdb_index_set_param", "vdb_index_get_stat",
-    "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_get_vectors",
+    "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
+    "vdb_index_get_vectors",
     "vdb_index_search", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
@@ -97,6 +98,7 @@ def load_library():
             "vdb_index_count": (c_i32, [c_vp, p_i64]),
             "vdb_index_clear": (c_i32, [c_vp]),
             "vdb_index_remove": (c_i32, [c_vp, c_vp, c_i32, c_vp, p_i64]),
+            "vdb_index_update": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
             "vdb_index_get_vectors": (c_i32, [c_vp, c_i64, c_i64, c_vp]),
             "vdb_index_search": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
@@ -260,6 +262,30 @@ class NativeIndex:
         _check(self._lib.vdb_index_remove(self._h, ctypes.c_void_p(mask_ptr or None), MEM_DEVICE,
                                           ctypes.c_void_p(stream or None), ctypes.byref(n)))
         return int(n.value)
+
+    def update(self, rows, vectors: np.ndarray) -> int:
+        """include/vdb.h vdb_index_update: row rows[i] becomes vectors[i], in place.  ``rows``:
+        integer row ids (any integer dtype, any order, pairwise distinct); ``vectors``: shape
+        (len(rows), dim).  Returns the number of rows updated.  An id outside [0, count), a
+        repeated id or a non-finite value raises ValueError and changes nothing."""
+        r = np.asarray(rows)
+        if r.size and r.dtype.kind not in "iu":
+            raise ValueError(f"row ids must be integers, got dtype {r.dtype}")
+        r = np.ascontiguousarray(r.reshape(-1), dtype=np.int64)
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 2 or v.shape != (r.size, self.dim):
+            raise ValueError(f"vectors must have shape ({r.size}, {self.dim}), got {v.shape}")
+        if r.size == 0:
+            return 0
+        _check(self._lib.vdb_index_update(self._h, _ptr(r), _ptr(v), r.size, MEM_HOST, None))
+        return int(r.size)
+
+    def update_device(self, rows_ptr: int, vectors_ptr: int, n: int, stream: int = 0) -> int:
+        """vdb_index_update with device-memory arguments (int64 ids and fp32 rows), read after the
+        work queued on ``stream``."""
+        _check(self._lib.vdb_index_update(self._h, ctypes.c_void_p(rows_ptr or None), ctypes.c_void_p(vectors_ptr or None),
+                                          int(n), MEM_DEVICE, ctypes.c_void_p(stream or None)))
+        return int(n)
 
     def get_vectors(self, start: int = 0, n: Optional[int] = None) -> np.ndarray:
         total = self.count()

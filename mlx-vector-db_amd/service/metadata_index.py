@@ -114,6 +114,70 @@ class MetadataIndex:
             self._n = n - int(ids.size)
             return int(ids.size)
 
+    def rows_with(self, key: Any, value: Any) -> np.ndarray:
+        """Sorted rows whose metadata has ``key`` with a value equal to ``value`` (dict-lookup
+        equality, as the postings keep it), straight from the postings: no bitmap is built.  A
+        row lacking the key never matches (unlike a filter on None); an unhashable or NaN value
+        is held by no posting and matches nothing."""
+        with self._lock:
+            if not (_hashable(key) and _hashable(value)):
+                return np.zeros(0, np.int64)
+            lst = self._post.get(key, {}).get(value)
+            if lst is None:
+                return np.zeros(0, np.int64)
+            return np.sort(np.frombuffer(lst, dtype=np.int64))
+
+    def replace(self, rows, metadata: List[Dict]) -> None:
+        """Row rows[i] now has metadata[i] (ids in [0, len), pairwise distinct): the postings lose
+        the old dicts' pairs and gain the new ones', O(pairs of those rows) dictionary work plus
+        one pass over each posting list touched; no row is renumbered.  Every cached bitmap is
+        dropped (called under the store's write lock)."""
+        with self._lock:
+            ids = [int(r) for r in np.asarray(rows, dtype=np.int64).reshape(-1)]
+            if len(ids) != len(metadata):
+                raise ValueError(f"{len(ids)} rows but {len(metadata)} metadata entries")
+            if len(set(ids)) != len(ids):
+                raise ValueError("row ids must be pairwise distinct")
+            if ids and (min(ids) < 0 or max(ids) >= self._n):
+                raise ValueError(f"row ids must be in [0, {self._n}), got [{min(ids)}, {max(ids)}]")
+            self._cache.clear()
+            if len(self._rows) < self._n:  # (fewer metadata entries than rows: the rest hold nothing)
+                self._rows.extend({} for _ in range(self._n - len(self._rows)))
+            lose: Dict[Tuple[Any, Any], set] = {}
+            gain: Dict[Tuple[Any, Any], List[int]] = {}
+            for r, new in zip(ids, metadata):
+                old = self._rows[r]
+                op = {(k, v) for k, v in old.items() if _hashable(v)} if isinstance(old, dict) else set()
+                np_ = {(k, v) for k, v in new.items() if _hashable(v)} if isinstance(new, dict) else set()
+                for kv in op - np_:  # (a pair both dicts hold keeps its posting entry)
+                    lose.setdefault(kv, set()).add(r)
+                for kv in np_ - op:
+                    gain.setdefault(kv, []).append(r)
+                self._rows[r] = new
+            for (k, v), gone in lose.items():
+                by_val = self._post.get(k)
+                lst = by_val.get(v) if by_val is not None else None
+                if lst is None:
+                    continue
+                a = np.frombuffer(lst, dtype=np.int64)
+                a = a[~np.isin(a, np.fromiter(gone, dtype=np.int64, count=len(gone)))]
+                if a.size:
+                    kept = array("q")
+                    kept.frombytes(a.astype(np.int64).tobytes())
+                    by_val[v] = kept
+                else:
+                    del by_val[v]
+                    if not by_val:
+                        del self._post[k]
+            for (k, v), add in gain.items():
+                by_val = self._post.setdefault(k, {})
+                lst = by_val.get(v)
+                a = np.frombuffer(lst, dtype=np.int64) if lst is not None else np.zeros(0, np.int64)
+                a = np.union1d(a, np.asarray(add, dtype=np.int64))  # postings stay sorted
+                merged = array("q")
+                merged.frombytes(a.astype(np.int64).tobytes())
+                by_val[v] = merged
+
     def _pair_rows(self, key: Any, value: Any, n: int) -> np.ndarray:
         """Sorted rows < n with ``meta.get(key) == value``."""
         # rows past the metadata list (the reference allows fewer metadata entries than vectors;

@@ -298,31 +298,35 @@ class MLXVectorStore:
     def add_vectors(self, vectors: Union[np.ndarray, Any], metadata: List[Dict]):
         """service/optimized_vector_store.py:96-114."""
         with self._lock, _Write(self._rw):
-            v = _as_matrix(vectors)
-            if v.ndim == 1:
-                v = v[None, :]
-            if v.ndim != 2:
-                raise ValueError(f"vectors must be 2-D (n, dim), got shape {v.shape}")
-            n0 = self._vector_count
-            if v.shape[0] > 0:
-                self._ensure_index(v.shape[1]).add(v)
-            self._metadata.extend(metadata)
-            # the filter postings index exactly the rows' metadata (row r <-> metadata[r])
-            self._meta_index.extend(self._metadata[len(self._meta_index):])
-            self._vector_count = self._index.count() if self._index is not None else 0
-            self._is_dirty = True
-            if self.config.persist and v.shape[0] > 0:
-                # O(new rows) append instead of the reference's full rewrite per add (:113, :218-223)
-                self._files.append(v, metadata)
-                if self._files.needs_compaction():
-                    self._save_store(force=True)
-                else:
-                    self._is_dirty = False
-            if self.config.enable_hnsw and self._hnsw_index is not None and self._index is not None:
-                # the reference rebuilds the graph from scratch on every add (:110-112); the graph
-                # path inserts the new rows into the existing graph instead (performance/hnsw_index.py)
-                self._hnsw_index.add_rows(self._index, n0)
-            return {"vectors_added": len(metadata), "total_vectors": self._vector_count}
+            return self._add_locked(vectors, metadata)
+
+    def _add_locked(self, vectors, metadata: List[Dict]):
+        """add_vectors with the write locks held."""
+        v = _as_matrix(vectors)
+        if v.ndim == 1:
+            v = v[None, :]
+        if v.ndim != 2:
+            raise ValueError(f"vectors must be 2-D (n, dim), got shape {v.shape}")
+        n0 = self._vector_count
+        if v.shape[0] > 0:
+            self._ensure_index(v.shape[1]).add(v)
+        self._metadata.extend(metadata)
+        # the filter postings index exactly the rows' metadata (row r <-> metadata[r])
+        self._meta_index.extend(self._metadata[len(self._meta_index):])
+        self._vector_count = self._index.count() if self._index is not None else 0
+        self._is_dirty = True
+        if self.config.persist and v.shape[0] > 0:
+            # O(new rows) append instead of the reference's full rewrite per add (:113, :218-223)
+            self._files.append(v, metadata)
+            if self._files.needs_compaction():
+                self._save_store(force=True)
+            else:
+                self._is_dirty = False
+        if self.config.enable_hnsw and self._hnsw_index is not None and self._index is not None:
+            # the reference rebuilds the graph from scratch on every add (:110-112); the graph
+            # path inserts the new rows into the existing graph instead (performance/hnsw_index.py)
+            self._hnsw_index.add_rows(self._index, n0)
+        return {"vectors_added": len(metadata), "total_vectors": self._vector_count}
 
     # ---- delete ----------------------------------------------------------------------
     def delete_vectors(self, filter_metadata: Optional[Dict]) -> Dict[str, int]:
@@ -387,6 +391,116 @@ class MLXVectorStore:
             if self._vector_count:
                 self._hnsw_index.build(None, native_index=self._index)
         return {"deleted": int(deleted), "total_vectors": self._vector_count}
+
+    # ---- update ----------------------------------------------------------------------
+    def update_rows(self, indices, vectors, metadata: Optional[List[Dict]] = None) -> Dict[str, int]:
+        """Replace rows in place, by position: row indices[i] becomes vectors[i] (and, with
+        ``metadata``, a list of the same length, takes metadata[i]; otherwise the rows keep
+        theirs).  No row moves or is renumbered (include/vdb.h vdb_index_update).  Ids outside
+        [0, count) or repeated raise ValueError with store and index unchanged."""
+        self._check_can_update()
+        with self._lock, _Write(self._rw):
+            ids, v = self._check_update_args(indices, vectors, metadata)
+            if ids.size:
+                self._update_locked(ids, v, metadata)
+            return {"updated": int(ids.size), "total_vectors": self._vector_count}
+
+    def upsert_vectors(self, vectors, metadata: List[Dict], key: str = "id") -> Dict[str, int]:
+        """Insert or replace by ``metadata[key]``: an item whose key value one stored row holds
+        replaces that row's vector and metadata in place (one device update for all such items);
+        the others are appended in their given order (one add).  The reference store has no
+        counterpart; its benchmark calls ``upsert`` on the database it compares itself with
+        (benchmarks/benchmark_app.py:104).  Raises ValueError before anything changes for an item
+        without ``key``, two items with the same key value, or a key value more than one stored
+        row holds."""
+        self._check_can_update()
+        with self._lock, _Write(self._rw):
+            v = _as_matrix(vectors)
+            if v.ndim == 1:
+                v = v[None, :]
+            if v.ndim != 2:
+                raise ValueError(f"vectors must be 2-D (n, dim), got shape {v.shape}")
+            if len(metadata) != v.shape[0]:
+                raise ValueError(f"{v.shape[0]} vectors but {len(metadata)} metadata entries")
+            if self._dim is not None and v.shape[0] and v.shape[1] != self._dim:
+                raise ValueError(f"Dimension mismatch: store holds {self._dim}-d vectors, got {v.shape[1]}-d")
+            seen = set()
+            hit_items, hit_rows, new_items = [], [], []
+            for i, m in enumerate(metadata):
+                if not isinstance(m, dict) or key not in m:
+                    raise ValueError(f"upsert item {i} has no metadata key {key!r}")
+                kv = m[key]
+                try:
+                    dup = kv in seen
+                    seen.add(kv)
+                except TypeError:
+                    raise ValueError(f"upsert item {i}: {key!r} value {kv!r} is not hashable") from None
+                if dup:
+                    raise ValueError(f"upsert items share the {key!r} value {kv!r}")
+                rows = self._meta_index.rows_with(key, kv)
+                if rows.size > 1:
+                    raise ValueError(f"{rows.size} stored rows hold the {key!r} value {kv!r}")
+                if rows.size == 1:
+                    hit_items.append(i)
+                    hit_rows.append(int(rows[0]))
+                else:
+                    new_items.append(i)
+            if not np.isfinite(v).all():  # (the device would reject the update or the add alone)
+                raise ValueError("vectors contain NaN or Inf; nothing was changed")
+            if hit_items:
+                self._update_locked(np.asarray(hit_rows, np.int64), v[hit_items], [metadata[i] for i in hit_items],
+                                    save=not new_items)
+            if new_items:
+                self._add_locked(v[new_items], [metadata[i] for i in new_items])
+                if hit_items and self.config.persist:
+                    # the append log cannot record an update: the base files take both at once
+                    self._is_dirty = True
+                    self._save_store(force=True)
+            return {"updated": len(hit_items), "added": len(new_items), "total_vectors": self._vector_count}
+
+    def _check_can_update(self):
+        if len(self._devices()) > 1:
+            raise NotImplementedError("update is not supported on a multi-device store")
+
+    def _check_update_args(self, indices, vectors, metadata) -> Tuple[np.ndarray, np.ndarray]:
+        n = self._vector_count
+        ids = np.asarray(indices).reshape(-1)
+        if ids.size and ids.dtype.kind not in "iu":
+            raise ValueError(f"row ids must be integers, got dtype {ids.dtype}")
+        ids = ids.astype(np.int64)
+        v = _as_matrix(vectors)
+        if v.ndim == 1:
+            v = v[None, :]
+        if v.ndim != 2 or v.shape[0] != ids.size:
+            raise ValueError(f"vectors must have shape ({ids.size}, dim), got {v.shape}")
+        if metadata is not None and len(metadata) != ids.size:
+            raise ValueError(f"{ids.size} rows but {len(metadata)} metadata entries")
+        if ids.size:
+            if int(ids.min()) < 0 or int(ids.max()) >= n:
+                raise ValueError(f"row ids must be in [0, {n}), got [{int(ids.min())}, {int(ids.max())}]")
+            if np.unique(ids).size != ids.size:
+                raise ValueError("row ids must be pairwise distinct")
+            if v.shape[1] != self._dim:
+                raise ValueError(f"Dimension mismatch: store holds {self._dim}-d vectors, got {v.shape[1]}-d")
+        return ids, v
+
+    def _update_locked(self, ids: np.ndarray, v: np.ndarray, metadata: Optional[List[Dict]], save: bool = True):
+        """Rows ids := v on the device, then their metadata (write locks held, arguments checked:
+        the device call rejects what is left, a non-finite value, before it writes)."""
+        self._index.update(ids, v)
+        if metadata is not None:
+            if len(self._metadata) < self._vector_count:
+                self._metadata.extend({} for _ in range(self._vector_count - len(self._metadata)))
+            for r, m in zip(ids.tolist(), metadata):
+                self._metadata[r] = m
+            self._meta_index.replace(ids, metadata)
+        self._is_dirty = True
+        if self.config.persist and save:
+            # delete's cost model: a full rewrite of the base files (the append log has no update record)
+            self._save_store(force=True)
+        if self.config.enable_hnsw and self._hnsw_index is not None and self._vector_count:
+            # the graph is stale by generation: rebuilt from the index, as after a delete
+            self._hnsw_index.build(None, native_index=self._index)
 
     # ---- query ---------------------------------------------------------------------
     def query(self, query_vector: Union[np.ndarray, Any], k: int = 10,
@@ -630,6 +744,10 @@ def _get_store(user_id: str, model_id: str) -> MLXVectorStore:
 
 def add_vectors(user_id: str, model_id: str, vectors, metadata: List[Dict]) -> Dict[str, int]:
     return _get_store(user_id, model_id).add_vectors(vectors, metadata)
+
+
+def upsert_vectors(user_id: str, model_id: str, vectors, metadata: List[Dict], key: str = "id") -> Dict[str, int]:
+    return _get_store(user_id, model_id).upsert_vectors(vectors, metadata, key=key)
 
 
 def query_vectors(user_id: str, model_id: str, query_vector, k: int = 10,
