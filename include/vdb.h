@@ -146,7 +146,9 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "finish_split", "finish_small" (-1 auto: the finish's 4-wave form beside a long-row
  * wide scan for batches of >= 32, 0 off, 1 on), "i8_refine", "i8_narrow", "device_repass", "auto_int8", "auto_i8q",
  * "dir_bound" (0: BF16 certificate with |q| R only), "remove_chunk" / "update_chunk" (rows per
- * chunk of vdb_index_remove's scratch / vdb_index_update's staging, 0 = by bytes).  Stats also: "searches", "queries",
+ * chunk of vdb_index_remove's scratch / vdb_index_update's staging, 0 = by bytes), "subset_wgs"
+ * (workgroups per query of vdb_index_search_rows, 0 = auto; its stats "subset_searches",
+ * "subset_queries", "subset_rows", "subset_bad_ids" are described there).  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -235,6 +237,45 @@ int32_t vdb_index_search(vdb_index* idx, const float* queries, int32_t n_queries
                          const uint32_t* row_mask, int32_t mem,
                          float* out_scores, int64_t* out_indices, double* out_keys,
                          int64_t index_offset, void* stream);
+
+/* Search explicit row-id lists, one per query or shared between queries: only the listed rows
+ * are scored, exactly, so a selective filter costs its own rows and not a pass over the corpus.
+ * Replaces: the reference's O(N) metadata scan plus masked argsort
+ * (service/optimized_vector_store.py:159-183), for which vdb_index_search's row_mask is the
+ * whole-corpus form: one bitmap for the batch, every row streamed.
+ *   list_offsets [n_lists + 1] int64, list_rows [n_ids] int64: the candidate sets in CSR form,
+ *                list l = list_rows[list_offsets[l] .. list_offsets[l+1]), offsets ascending
+ *                from >= 0 to <= n_ids, each list strictly ascending row ids in [0, count).
+ *                An empty list is valid (every slot of its queries is "no result").
+ *   n_ids        host scalar, the length of list_rows: the launch is sized from it, so a
+ *                device-memory call reads nothing back.
+ *   query_list   [n_queries] int32, query b searches list query_list[b]; several queries may
+ *                share a list.  NULL = query b searches list b (n_lists == n_queries).
+ *   queries, k, mem, out_*, index_offset, stream: as vdb_index_search; all pointers of one
+ *                memory kind.  n_queries == 0 is VDB_OK.
+ * Result: that of vdb_index_search over row_mask = exactly the list's set, bit for bit --
+ * ranking by the canonical fp64 key, ties to the lower row, scores the key rounded to fp32, slots
+ * past min(k, list length) index -1 / score 0 / key -inf -- for every precision setting: the
+ * rows come from the row-major fp32 copy and the candidate copies are not read.
+ * One launch per call plus the query norms: grid (workgroups per query, queries), a wave per
+ * row, per-wave streaming top-k, and the workgroup that finishes a query last merges its lists.
+ * Host-memory calls are validated before anything is launched: offsets that decrease or pass
+ * n_ids, an id outside [0, count), a list not strictly ascending, a query_list entry outside
+ * [0, n_lists) -> VDB_ERR_INVALID; NaN / Inf in a query -> VDB_ERR_NONFINITE.  A device-memory
+ * call cannot be validated without a sync, so the kernel handles such input itself: offsets are
+ * clamped to [0, n_ids], a query whose query_list entry is out of range gets an empty result,
+ * and an id outside [0, count) or not greater than the entry before it in its list is skipped
+ * and counted (stat "subset_bad_ids", once per query that meets it); nothing out of bounds is
+ * read.  Takes the index's shared lock, a per-search workspace and its stream as a search does
+ * (add / remove / update / clear wait for queued calls).  Stats (cumulative, successful calls):
+ * "subset_searches", "subset_queries", "subset_rows" (ids offered), "subset_bad_ids".  Knob
+ * "subset_wgs": workgroups per query, 0 = auto from n_ids over the lists (or queries, if fewer)
+ * and the CU count; results are identical for every value. */
+int32_t vdb_index_search_rows(vdb_index* idx, const float* queries, int32_t n_queries, int32_t k,
+                              const int64_t* list_offsets, int32_t n_lists, const int64_t* list_rows, int64_t n_ids,
+                              const int32_t* query_list, int32_t mem,
+                              float* out_scores, int64_t* out_indices, double* out_keys,
+                              int64_t index_offset, void* stream);
 
 /* --- multi-GPU merge -----------------------------------------------------------
  * Merge per-shard top-k lists (all device memory, already all-gathered):

@@ -6,7 +6,7 @@ and HTTP scripts work unchanged:
 
   POST /vectors/add           {user_id, model_id, vectors, metadata}       (:163-207)
   POST /vectors/query         {user_id, model_id, query, k, filter_metadata} (:211-270)
-  POST /vectors/batch_query   {user_id, model_id, queries, k}              (:272-330)
+  POST /vectors/batch_query   {user_id, model_id, queries, k[, filter_metadata]}            (:272-330)
   GET  /vectors/count, /vectors/stats, /vectors/health                     (:332-388)
   POST /vectors/delete        {user_id, model_id, filter_metadata} -> {deleted}: the call the
                               SDK's delete_vectors_by_metadata makes
@@ -37,7 +37,7 @@ import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
-from typing import Any, Callable, Dict, List, Optional
+from typing import Any, Callable, Dict, List, Optional, Union
 
 from fastapi import APIRouter, Depends, HTTPException, Security
 from fastapi.security import HTTPAuthorizationCredentials, HTTPBearer
@@ -75,6 +75,8 @@ class BatchQueryRequest(BaseModel):
     model_id: str
     queries: List[List[float]]
     k: int = 10
+    # one filter for every query, or one entry (a filter or null) per query
+    filter_metadata: Optional[Union[Dict[str, Any], List[Optional[Dict[str, Any]]]]] = None
 
 
 class VectorDeleteRequest(BaseModel):
@@ -291,9 +293,14 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
             store = await mgr.get_store(request.user_id, request.model_id)
             if not request.queries:
                 raise HTTPException(status_code=400, detail="Query vectors required")
+            filt = request.filter_metadata
+            if isinstance(filt, list) and len(filt) != len(request.queries):
+                raise HTTPException(status_code=400,
+                                    detail=f"{len(request.queries)} queries but {len(filt)} filters")
+            kw = {} if filt is None else {"filter_metadata": filt}  # (without one: the call as it always was)
             loop = asyncio.get_running_loop()
             batch = await loop.run_in_executor(mgr._executor,
-                                               lambda: store.batch_query(request.queries, k=request.k))
+                                               lambda: store.batch_query(request.queries, k=request.k, **kw))
             total = (time.time() - t0) * 1000
             return BatchQueryResponse(results=format_batch_results(store.config.metric, batch),
                                       total_queries=len(request.queries),

@@ -23,6 +23,7 @@
 
 #include "../../include/vdb.h"
 #include "vdb_compact_plan.h"
+#include "vdb_subset_plan.h"
 #include "vdb_internal.h"
 
 using namespace vdb;
@@ -53,6 +54,7 @@ constexpr int64_t kRowAlign = ROW_ALIGN;   // capacity granule, a multiple of ev
 
 constexpr size_t kGatedExactBytes = 256u << 20;  // device-gated fallback lists sized for every query of a batch
 constexpr int kMaxApproxK = 200;          // k above this uses the exact path
+constexpr int kSubsetBadWord = 12;        // d_xmax word (8 bytes each) counting a row-list search's skipped ids
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 inline int next_pow2(int v) {
@@ -224,6 +226,10 @@ struct vdb_index {
     std::atomic<int64_t> n_xs_builds{0};  // lazy builds of the split copy (ensure_xs)
     std::atomic<int64_t> n_rows_removed{0};  // rows removed by vdb_index_remove (cumulative)
     std::atomic<int64_t> n_rows_updated{0};  // rows rewritten by vdb_index_update (cumulative)
+    // vdb_index_search_rows: calls, queries and ids offered (successful calls); the ids a
+    // device-memory call's kernel skipped are counted on the device (d_xmax + kSubsetBadWord)
+    std::atomic<int64_t> n_subset_searches{0}, n_subset_queries{0}, n_subset_rows{0};
+    int64_t subset_wgs = 0;  // knob: workgroups per query of a row-list search (0 = auto)
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -697,7 +703,7 @@ extern "C" {
 
 const char* vdb_last_error(void) { return g_last_error.c_str(); }
 
-int32_t vdb_version(void) { return 1; }
+int32_t vdb_version(void) { return 2; }
 
 int32_t vdb_device_count(int32_t* n) {
     int c = 0;
@@ -734,7 +740,8 @@ int32_t vdb_index_create(int32_t dim, int32_t metric, int32_t device, vdb_index*
     if (const char* a8 = std::getenv("VDB_AUTO_I8")) ix->auto_i8 = std::atoi(a8) != 0;
     hipError_t e = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
     // d_xmax: [0, 32) the residual maxima, [32, 36) the non-finite count, [64, 96) and
-    // [128, 192) an add's snapshot of the maxima and of d_i8 (restored when the add is rejected)
+    // [128, 192) an add's snapshot of the maxima and of d_i8 (restored when the add is rejected),
+    // [96, 104) the ids row-list searches skipped (kSubsetBadWord; cumulative, a clear keeps it)
     if (e == hipSuccess) e = hipMalloc(&ix->d_xmax, 192);
     if (e == hipSuccess) e = zero_now(ix->d_xmax, 192, ix->stream);
     if (e == hipSuccess) e = hipMalloc(&ix->d_i8, 64);
@@ -913,6 +920,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
         if (value < 0) return set_error(VDB_ERR_INVALID, "update_chunk must be >= 0 (0 = sized by bytes)");
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->update_chunk = value;
+    } else if (n == "subset_wgs") {
+        if (value < 0 || value > kSubsetMaxSeg)
+            return set_error(VDB_ERR_INVALID, "subset_wgs must be in [0, %d] (0 = auto)", kSubsetMaxSeg);
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->subset_wgs = value;
     } else if (n == "device_repass") {
         if (value < -1 || value > 1) return set_error(VDB_ERR_INVALID, "device_repass must be -1, 0 or 1");
         ix->device_repass = value;
@@ -1006,6 +1018,17 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "split_copy_builds") *value = ix->n_xs_builds.load();
     else if (n == "rows_removed") *value = ix->n_rows_removed.load();
     else if (n == "rows_updated") *value = ix->n_rows_updated.load();
+    else if (n == "subset_searches") *value = ix->n_subset_searches.load();
+    else if (n == "subset_queries") *value = ix->n_subset_queries.load();
+    else if (n == "subset_rows") *value = ix->n_subset_rows.load();
+    else if (n == "subset_bad_ids") {  // counted by the kernel: after the row-list searches queued so far
+        HIP_TRY(hipSetDevice(ix->device));
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpy(&bad, ix->d_xmax + kSubsetBadWord, sizeof(bad), hipMemcpyDeviceToHost));
+        *value = (int64_t)bad;
+    }
     else return set_error(VDB_ERR_INVALID, "unknown stat '%s'", name);
     return VDB_OK;
 }
@@ -2314,6 +2337,140 @@ int32_t vdb_shutdown(void) {
         hipMemPool_t pool = nullptr;
         if (hipDeviceGetDefaultMemPool(&pool, d) == hipSuccess && pool) (void)hipMemPoolTrimTo(pool, 0);
     }
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_rows(vdb_index* ix, const float* queries, int32_t B, int32_t k, const int64_t* list_offsets,
+                              int32_t n_lists, const int64_t* list_rows, int64_t n_ids, const int32_t* query_list,
+                              int32_t mem, float* out_scores, int64_t* out_indices, double* out_keys,
+                              int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (B == 0) return VDB_OK;
+    if (B < 0) return set_error(VDB_ERR_INVALID, "n_queries must be >= 0, got %d", B);
+    if (k <= 0 || k > 1024) return set_error(VDB_ERR_INVALID, "k must be in [1, 1024], got %d", k);
+    if (!queries || !out_scores || !out_indices) return set_error(VDB_ERR_INVALID, "NULL query/output pointer");
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    if (n_lists < 0 || n_ids < 0) return set_error(VDB_ERR_INVALID, "n_lists and n_ids must be >= 0");
+    if (!list_offsets || (n_ids > 0 && !list_rows)) return set_error(VDB_ERR_INVALID, "NULL list pointer");
+    if (!query_list && n_lists != B)
+        return set_error(VDB_ERR_INVALID, "without a query_list n_lists (%d) must equal n_queries (%d)", n_lists, B);
+    const int D = ix->dim;
+    if (mem == VDB_MEM_HOST && !all_finite(queries, (int64_t)B * D))
+        return set_error(VDB_ERR_NONFINITE, "query contains NaN or Inf");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    if (mem == VDB_MEM_HOST) {  // everything checked before any launch
+        int64_t at = 0;
+        switch (subset_validate(list_offsets, n_lists, list_rows, n_ids, query_list, B, N, &at)) {
+            case kSubsetOk: break;
+            case kSubsetBadOffsets:
+                return set_error(VDB_ERR_INVALID, "list_offsets[%lld] = %lld: offsets must ascend from >= 0 to <= n_ids (%lld)",
+                                 (long long)at, (long long)list_offsets[at], (long long)n_ids);
+            case kSubsetBadId:
+                return set_error(VDB_ERR_INVALID, "list_rows[%lld] = %lld is outside [0, %lld)", (long long)at,
+                                 (long long)list_rows[at], (long long)N);
+            case kSubsetUnsorted:
+                return set_error(VDB_ERR_INVALID, "list_rows[%lld] = %lld: a list must be strictly ascending", (long long)at,
+                                 (long long)list_rows[at]);
+            case kSubsetBadQueryList:
+                return set_error(VDB_ERR_INVALID, "query_list[%lld] = %d is outside [0, %d)", (long long)at,
+                                 query_list[at], n_lists);
+            default:
+                return set_error(VDB_ERR_INVALID, "without a query_list n_lists must equal n_queries");
+        }
+    }
+    // as a search: the caller's stream (device memory: NULL = the null stream), or for a
+    // host-memory call without one the stream of the workspace it takes
+    const bool own_stream = mem == VDB_MEM_HOST && !stream;
+    hipStream_t st = own_stream ? nullptr : (hipStream_t)stream;
+    Workspace* w = acquire_ws(ix, st, own_stream);
+    if (own_stream) {
+        if (!w->own) {
+            const hipError_t e = hipStreamCreateWithFlags(&w->own, hipStreamNonBlocking);
+            if (e != hipSuccess) {
+                std::lock_guard<std::mutex> lg(ix->ws_mu);
+                w->busy = false;
+                return set_error(VDB_ERR_HIP, "workspace stream: %s", hipGetErrorString(e));
+            }
+        }
+        st = w->own;
+    }
+    struct Releaser {
+        vdb_index* ix; Workspace* w; hipStream_t st;
+        ~Releaser() { release_ws(ix, w, st); }
+    } rel{ix, w, st};
+
+    const bool host = mem == VDB_MEM_HOST;
+    const int KE = subset_ke(k);
+    const int n_seg = N > 0 ? subset_n_seg(ix->subset_wgs, n_ids, B, n_lists, ix->n_cu) : 1;
+    const SubsetScratch sc = subset_scratch(B, D, k, n_seg, n_lists, n_ids, host, query_list != nullptr, out_keys != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    SubsetArgs a{};
+    a.Q = queries;
+    a.offs = list_offsets;
+    a.rows = list_rows;
+    a.qlist = query_list;
+    a.out_s = out_scores;
+    a.out_i = out_indices;
+    a.out_k = out_keys;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = ws_host_io(w, (size_t)(sc.in_bytes + sc.out_bytes));
+        if (rc) return rc;
+        char* h = w->host_io;
+        std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+        std::memcpy(h + (sc.offs - sc.in0), list_offsets, ((size_t)n_lists + 1) * 8);
+        if (n_ids > 0) std::memcpy(h + (sc.rows - sc.in0), list_rows, (size_t)n_ids * 8);
+        if (query_list) std::memcpy(h + (sc.qlist - sc.in0), query_list, (size_t)B * 4);
+        HIP_TRY(hipMemcpyAsync(dev + sc.in0, h, (size_t)sc.in_bytes, hipMemcpyHostToDevice, st));
+        a.Q = reinterpret_cast<const float*>(dev + sc.q);
+        a.offs = reinterpret_cast<const int64_t*>(dev + sc.offs);
+        a.rows = reinterpret_cast<const int64_t*>(dev + sc.rows);
+        a.qlist = query_list ? reinterpret_cast<const int32_t*>(dev + sc.qlist) : nullptr;
+        a.out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_k = out_keys ? reinterpret_cast<double*>(dev + sc.out_k) : nullptr;
+    }
+    if (N == 0) {  // an empty index: every slot "no result", as a search
+        HIP_TRY(launch_empty_results((int64_t)B * k, a.out_s, a.out_i, a.out_k, st));
+    } else {
+        double* qn64 = reinterpret_cast<double*>(dev + sc.qn64);
+        int* done = reinterpret_cast<int*>(dev + sc.done);
+        // the canonical query norms and the zeroed per-query counters, nothing else: no query tiles
+        HIP_TRY(launch_prep_queries(a.Q, B, B, D, ix->G, ix->metric, nullptr, nullptr, qn64, nullptr, nullptr, nullptr,
+                                    nullptr, done, st));
+        a.qn64 = qn64;
+        a.X = ix->X;
+        a.G = ix->G;
+        a.D = D;
+        a.nrm64 = ix->nrm64;
+        a.count = N;
+        a.n_lists = n_lists;
+        a.n_ids = n_ids;
+        a.k = k;
+        a.KE = KE;
+        a.lk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.lk) : nullptr;
+        a.li = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.li) : nullptr;
+        a.mk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.mk) : nullptr;
+        a.mi = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.mi) : nullptr;
+        a.done = done;
+        a.bad = ix->d_xmax + kSubsetBadWord;
+        a.index_offset = index_offset;
+        HIP_TRY(launch_subset_search(ix->metric, a, B, n_seg, st));
+    }
+    if (host) {
+        char* r = w->host_io + sc.in_bytes;
+        HIP_TRY(hipMemcpyAsync(r, dev + sc.out0, (size_t)sc.out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+        if (out_keys) std::memcpy(out_keys, r + (sc.out_k - sc.out0), (size_t)B * k * 8);
+    }
+    ix->n_subset_searches++;
+    ix->n_subset_queries += B;
+    ix->n_subset_rows += n_ids;
     return VDB_OK;
 }
 

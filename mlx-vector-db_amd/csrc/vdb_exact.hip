@@ -4,55 +4,9 @@
 #include "vdb_internal.h"
 #include <type_traits>
 #include "vdb_merge_block.h"
+#include "vdb_exact_keys.h"  // exact_key, exact_keys_rows, exact_keys_batch
 
 namespace vdb {
-
-// =============================================================================
-// Exact fp64 keys
-// =============================================================================
-// key(q, r): cosine  dot / (max(|q|,1e-8) * max(|x|,1e-8))
-//            L2      -(sum (x-q)^2)
-// in the canonical order (vdb_common.h).  One wave per (query, row); up to four
-// 16-byte corpus pieces per lane in flight.
-template <int METRIC>
-__device__ __forceinline__ double exact_key(const float* __restrict__ q, double qn, const float* __restrict__ X, int G,
-                                            int D, uint64_t r, double xn) {
-    const int lane = threadIdx.x & 63;
-    const int Dp = G * GROUP_DIMS;
-    const int np = (D + 255) / 256;
-    double acc = 0.0;
-    for (int m0 = 0; m0 < np; m0 += 4) {
-        f32x4 xv[4];
-        float qv[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int p = (m0 + u) * 64 + lane;
-            const bool in = (m0 + u) < np;
-            xv[u] = (in && 4 * p < Dp) ? *(const f32x4*)(X + row_piece_offset(r, p, G)) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) qv[u][j] = (in && 4 * p + j < D) ? q[4 * p + j] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if ((m0 + u) < np) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const double qd = (double)qv[u][j];
-                    const double xd = (double)xv[u][j];
-                    if (METRIC == 0) {
-                        acc = acc + qd * xd;
-                    } else {
-                        const double df = xd - qd;
-                        acc = acc + df * df;
-                    }
-                }
-            }
-        }
-    }
-    acc = wave_sum_butterfly(acc);
-    if (METRIC == 0) return acc / (fmax(qn, 1e-8) * fmax(xn, 1e-8));
-    return -acc;
-}
 
 // Rerank: exact keys of the KP candidates (16 waves, one candidate per wave at a
 // time), best k out, and the certificate that the exact top-k lies inside the
@@ -111,59 +65,7 @@ __device__ __forceinline__ void exact_keys_regs(const float (&qv)[MP][4], double
     }
 }
 
-// As exact_keys_regs for longer rows: every piece of the NB rows in flight at once, the query's
-// pieces read from memory (L1-resident) as each is consumed instead of held in registers.
-template <int METRIC, int NB, int MP>
-__device__ __forceinline__ void exact_keys_rows(const float* __restrict__ q, int D, double qn,
-                                                const float* __restrict__ X, int G, int np, const uint32_t* rows,
-                                                const double* xn, int nb, double* out) {
-    const int lane = threadIdx.x & 63;
-    const int Dp = G * GROUP_DIMS;
-    f32x4 xv[MP][NB];
-#pragma unroll
-    for (int m = 0; m < MP; ++m) {
-        const int p = m * 64 + lane;
-#pragma unroll
-        for (int u = 0; u < NB; ++u)
-            xv[m][u] = (m < np && u < nb && 4 * p < Dp) ? *(const f32x4*)(X + row_piece_offset(rows[u], p, G))
-                                                       : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    double acc[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) acc[u] = 0.0;
-#pragma unroll
-    for (int m = 0; m < MP; ++m) {
-        if (m < np) {
-            float qv[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int d = 4 * (m * 64 + lane) + j;
-                qv[j] = d < D ? q[d] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < NB; ++u)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const double qd = (double)qv[j];
-                    const double xd = (double)xv[m][u][j];
-                    if (METRIC == 0) {
-                        acc[u] = acc[u] + qd * xd;
-                    } else {
-                        const double df = xd - qd;
-                        acc[u] = acc[u] + df * df;
-                    }
-                }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int u = 0; u < NB; ++u) acc[u] = acc[u] + __shfl_xor(acc[u], off, 64);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (u < nb) out[u] = METRIC == 0 ? acc[u] / (fmax(qn, 1e-8) * fmax(xn[u], 1e-8)) : -acc[u];
-    }
-}
+// (for longer rows: exact_keys_rows, vdb_exact_keys.h)
 
 // waves of the finish's one workgroup per query (1024 threads: 128 VGPRs each)
 // 16 (1024 threads, 128 VGPRs, a few spills) measured faster than 8 (512 threads, no spills) on
@@ -293,48 +195,7 @@ __device__ unsigned long long g_fin_stamps[8192][16];
 #define FIN_STAMP(i) do { } while (0)
 #endif
 
-template <int METRIC, int NB>
-__device__ __forceinline__ void exact_keys_batch(const float* __restrict__ q, double qn, const float* __restrict__ X,
-                                                 int G, int D, const uint32_t* rows, const double* xn, int nb,
-                                                 double* out) {
-    const int lane = threadIdx.x & 63;
-    const int Dp = G * GROUP_DIMS;
-    const int np = (D + 255) / 256;
-    double acc[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) acc[u] = 0.0;
-    for (int m = 0; m < np; ++m) {
-        const int p = m * 64 + lane;
-        float qv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) qv[j] = 4 * p + j < D ? q[4 * p + j] : 0.0f;
-        f32x4 xv[NB];
-#pragma unroll
-        for (int u = 0; u < NB; ++u)
-            xv[u] = (u < nb && 4 * p < Dp) ? *(const f32x4*)(X + row_piece_offset(rows[u], p, G)) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < NB; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double qd = (double)qv[j];
-                const double xd = (double)xv[u][j];
-                if (METRIC == 0) {
-                    acc[u] = acc[u] + qd * xd;
-                } else {
-                    const double df = xd - qd;
-                    acc[u] = acc[u] + df * df;
-                }
-            }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int u = 0; u < NB; ++u) acc[u] = acc[u] + __shfl_xor(acc[u], off, 64);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (u < nb) out[u] = METRIC == 0 ? acc[u] / (fmax(qn, 1e-8) * fmax(xn[u], 1e-8)) : -acc[u];
-    }
-}
+// (rows of any length: exact_keys_batch, vdb_exact_keys.h)
 
 // FW waves per workgroup: 16 (FIN_WAVES), or 8 for rows of more than 1024 dims (no spills at the
 // 8-piece exact keys: C3 400-413 K -> 419-421 K QPS; C2 / C4 / C6 -0.5..-1% at 8, so they keep 16;

@@ -334,6 +334,25 @@ hipError_t launch_exact_scan(int metric, int KE, const float* Q, const double* q
 // of slots x n_wg workgroups and one tail-merge scratch per slot
 size_t exact_scan_scratch_bytes(int KE, int n_wg, int slots);
 
+// Exact search over row-id lists (vdb_subset.hip, vdb_index_search_rows): query b scores the rows
+// of list qlist[b] (b if qlist == nullptr), list l = rows[offs[l] .. offs[l + 1]) of n_ids ids in
+// all, and writes its best k by (exact key desc, row asc) as a masked search would.  Grid
+// (n_seg, n_queries); with n_seg > 1 the workgroup that finishes a query last merges the
+// segments' lists lk / li [n_queries][n_seg][KE] through mk / mi [n_queries][KE] (done
+// [n_queries]: zero on entry, zero again on exit).  Nothing outside [0, n_ids) of rows, [0,
+// n_lists] of offs or [0, count) of the index is read whatever the arguments hold; ids skipped as
+// ineligible (vdb_subset_plan.h subset_id_ok) are added to *bad.  count >= 1.
+struct SubsetArgs {
+    const float* Q; const double* qn64; const float* X; int G; int D; const double* nrm64; int64_t count;
+    const int64_t* offs; int n_lists; const int64_t* rows; int64_t n_ids; const int32_t* qlist;
+    int k; int KE;
+    double* lk; uint32_t* li; double* mk; uint32_t* mi; int* done;
+    unsigned long long* bad;
+    float* out_s; int64_t* out_i; double* out_k; int64_t index_offset;
+};
+size_t subset_lds_bytes(int KE, int n_seg);
+hipError_t launch_subset_search(int metric, const SubsetArgs& a, int n_queries, int n_seg, hipStream_t st);
+
 // Merge sorted fp64-key lists.  Element (q, j, e) lives at q*sq + j*sj + e, lists
 // have Lk entries; output [nq][KP] sorted.
 hipError_t launch_merge_f64_u32(int KP, const double* lk, const uint32_t* li, int n_lists, int Lk,

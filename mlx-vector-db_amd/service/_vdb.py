@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_set_param", "vdb_index_get_stat",
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
-    "vdb_index_search", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_search", "vdb_index_search_rows", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -101,6 +101,8 @@ def load_library():
             "vdb_index_update": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
             "vdb_index_get_vectors": (c_i32, [c_vp, c_i64, c_i64, c_vp]),
             "vdb_index_search": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+            "vdb_index_search_rows": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp,
+                                              c_vp, c_i64, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -175,6 +177,22 @@ def rows_to_bitmap(mask_or_rows, count: int) -> np.ndarray:
     bits = np.zeros(max(need, 1) * 32, np.uint8)
     bits[rows] = 1
     return np.packbits(bits, bitorder="little").view(np.uint32)
+
+
+def pack_row_lists(lists) -> Tuple[np.ndarray, np.ndarray]:
+    """A sequence of integer row-id arrays -> the CSR pair vdb_index_search_rows takes: int64
+    offsets [len(lists) + 1] and the lists' ids back to back (int64)."""
+    arrs = []
+    for a in lists:
+        a = np.asarray(a)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"row ids must be integers, got dtype {a.dtype}")
+        arrs.append(a.astype(np.int64, copy=False).reshape(-1))
+    offs = np.zeros(len(arrs) + 1, np.int64)
+    if arrs:
+        np.cumsum([a.size for a in arrs], out=offs[1:])
+    rows = np.concatenate(arrs) if arrs else np.zeros(0, np.int64)
+    return offs, np.ascontiguousarray(rows, dtype=np.int64)
 
 
 class NativeIndex:
@@ -327,6 +345,62 @@ class NativeIndex:
             self._h, ctypes.c_void_p(q_ptr), int(n_queries), int(k), ctypes.c_void_p(mask_ptr or None),
             MEM_DEVICE, ctypes.c_void_p(out_scores_ptr), ctypes.c_void_p(out_idx_ptr),
             ctypes.c_void_p(out_keys_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
+
+    def search_rows(self, queries: np.ndarray, k: int, lists, query_list=None, with_keys: bool = False,
+                    index_offset: int = 0):
+        """include/vdb.h vdb_index_search_rows, host memory: query b is searched over the rows of
+        ``lists[query_list[b]]`` (``lists[b]`` without a ``query_list``) only, exactly.  ``lists``: a
+        sequence of integer arrays, each strictly ascending row ids in [0, count), packed to CSR
+        here.  Returns what ``search`` with a ``row_mask`` of exactly that list's rows returns.  A
+        malformed list or ``query_list`` raises ValueError."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must have shape (B, {self.dim}), got {np.shape(queries)}")
+        offs, rows = pack_row_lists(lists)
+        ql = None
+        if query_list is not None:
+            ql = np.asarray(query_list)
+            if ql.size and ql.dtype.kind not in "iu":
+                raise ValueError(f"query_list must hold integers, got dtype {ql.dtype}")
+            if ql.reshape(-1).size != q.shape[0]:
+                raise ValueError(f"query_list needs {q.shape[0]} entries, got {ql.size}")
+            if ql.size and (int(ql.min()) < -2**31 or int(ql.max()) >= 2**31):
+                raise ValueError("query_list entries must fit int32")
+            ql = np.ascontiguousarray(ql.reshape(-1), dtype=np.int32)
+        return self.search_rows_csr(q, k, offs, rows, ql, with_keys=with_keys, index_offset=index_offset)
+
+    def search_rows_csr(self, q: np.ndarray, k: int, offsets: np.ndarray, rows: np.ndarray,
+                        query_list: Optional[np.ndarray] = None, with_keys: bool = False, index_offset: int = 0):
+        """``search_rows`` with the lists already in CSR form (int64 offsets [n_lists + 1] and rows,
+        int32 query_list or None), passed to the C-ABI as they are."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        ql = None if query_list is None else np.ascontiguousarray(query_list, dtype=np.int32).reshape(-1)
+        if offs.size < 1:
+            raise ValueError("offsets needs n_lists + 1 entries")
+        B, k = q.shape[0], int(k)
+        scores = np.empty((B, k), dtype=np.float32)
+        idx = np.empty((B, k), dtype=np.int64)
+        keys = np.empty((B, k), dtype=np.float64) if with_keys else None
+        _check(self._lib.vdb_index_search_rows(
+            self._h, _ptr(q), B, k, _ptr(offs), offs.size - 1, _ptr(rows) if rows.size else None, rows.size,
+            _ptr(ql) if ql is not None else None, MEM_HOST, _ptr(scores), _ptr(idx),
+            _ptr(keys) if keys is not None else None, int(index_offset), None))
+        return (scores, idx, keys) if with_keys else (scores, idx)
+
+    def search_rows_device(self, q_ptr: int, n_queries: int, k: int, offsets_ptr: int, n_lists: int, rows_ptr: int,
+                           n_ids: int, out_scores_ptr: int, out_idx_ptr: int, out_keys_ptr: int = 0,
+                           query_list_ptr: int = 0, index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_rows with device-memory arguments (int64 offsets and rows, int32
+        query_list); stream-ordered, nothing is validated on the host (include/vdb.h)."""
+        _check(self._lib.vdb_index_search_rows(
+            self._h, ctypes.c_void_p(q_ptr), int(n_queries), int(k), ctypes.c_void_p(offsets_ptr), int(n_lists),
+            ctypes.c_void_p(rows_ptr or None), int(n_ids), ctypes.c_void_p(query_list_ptr or None), MEM_DEVICE,
+            ctypes.c_void_p(out_scores_ptr), ctypes.c_void_p(out_idx_ptr), ctypes.c_void_p(out_keys_ptr or None),
+            int(index_offset), ctypes.c_void_p(stream or None)))
 
 
 class NativeShards:

@@ -202,6 +202,25 @@ class MetadataIndex:
             rows = np.union1d(rows, missing)
         return rows[rows < n]
 
+    def _match_rows(self, filt: Dict, n: int) -> np.ndarray:
+        """Sorted rows < n matching every pair of ``filt`` (the lock held)."""
+        rows = None
+        for k, v in filt.items():
+            pr = self._pair_rows(k, v, n)
+            rows = pr if rows is None else np.intersect1d(rows, pr, assume_unique=True)
+            if rows.size == 0:
+                break
+        if rows is None:
+            rows = np.arange(n, dtype=np.int64)
+        return rows
+
+    def rows(self, filt: Dict, n: int) -> np.ndarray:
+        """The rows < n matching every pair of ``filt``, ascending and unique (int64, the caller's
+        own copy): the set ``bitmap`` marks, as the row list the device's row-list search takes
+        (include/vdb.h vdb_index_search_rows).  O(matching rows); nothing is cached."""
+        with self._lock:
+            return np.array(self._match_rows(filt, n), dtype=np.int64)
+
     def bitmap(self, filt: Dict, n: int) -> Tuple[np.ndarray, int]:
         """(uint32 words of the rows < n matching every pair, match count)."""
         try:
@@ -213,14 +232,7 @@ class MetadataIndex:
             if ck is not None and ck in self._cache:
                 self._cache.move_to_end(ck)
                 return self._cache[ck]
-            rows = None
-            for k, v in filt.items():
-                pr = self._pair_rows(k, v, n)
-                rows = pr if rows is None else np.intersect1d(rows, pr, assume_unique=True)
-                if rows.size == 0:
-                    break
-            if rows is None:
-                rows = np.arange(n, dtype=np.int64)
+            rows = self._match_rows(filt, n)
             bits = np.zeros(((n + 31) // 32) * 32, dtype=bool)
             bits[rows] = True
             words = np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32)

@@ -46,6 +46,11 @@ logger = logging.getLogger("mlx_vector_db.optimized_store")
 _NO_OPERATOR_MSG = "Keine kompilierte Ähnlichkeitsfunktion verfügbar."
 
 
+# half the smallest measured crossover of the row-list search against the masked
+# search (0.0136 % of the rows: 1 M x 128 L2, 64 queries sharing one list)
+SUBSET_MAX_FRACTION_DEFAULT = 6.8e-5
+
+
 @dataclass
 class MLXVectorStoreConfig:
     """service/optimized_vector_store.py:51-56, plus two MI355X knobs."""
@@ -66,6 +71,23 @@ class MLXVectorStoreConfig:
     # a batch leader's wait for the rest of a wave of callers (C2, 4 threads, 2 in flight: 8.6-8.9 K
     # QPS at 300 us against 8.3 K without, profiles/r06_serve/serving.txt; a lone caller never waits)
     coalesce_linger_us: float = 300.0
+    # a filter whose eligible rows are at most this fraction of the store is searched as an explicit
+    # row list (include/vdb.h vdb_index_search_rows: only those rows are read, and queries with
+    # different filters share one call, so they coalesce too); above it, or on a multi-device store,
+    # as a row_mask over the whole corpus.  0 disables the row-list path.  Results are identical
+    # either way; the value is half the smaller measured crossover.
+    subset_max_fraction: float = SUBSET_MAX_FRACTION_DEFAULT
+
+
+def _filter_key(filt: Dict):
+    """Grouping key of a filter: equal for filters holding the same pairs (as the bitmap cache
+    keys them); a filter with an unhashable value is its own group."""
+    try:
+        key = tuple(sorted(filt.items(), key=lambda kv: repr(kv[0])))
+        hash(key)
+        return key
+    except TypeError:
+        return ("unhashable", id(filt))
 
 
 def _as_matrix(vectors: Any) -> np.ndarray:
@@ -150,11 +172,14 @@ class _QueryCoalescer:
     one k class (k <= 16 / <= 200 / larger: the candidate pass a batch runs depends on its
     largest k, so one caller's large k does not move its co-batched callers to a slower pass);
     each caller gets its own row and k (the exact order makes every caller's top-k the prefix
-    of the batch's).  Callers hold the store's read lock while they wait, so every query of a
-    batch sees the same rows."""
+    of the batch's).  A batch also holds either only unfiltered requests (``run(Q, k)``) or only
+    filtered ones whose filters the store searches as row lists (``run(Q, k, filters)``, one
+    filter per query in order: one device call whatever the filters are).  Callers hold the store's
+    read lock while they wait, so every query of a batch sees the same rows."""
 
     def __init__(self, run, max_batch: int = 64, max_inflight: int = 2, linger_us: float = 0.0):
-        self._run = run            # run(Q [B, D], k) -> [(indices, scores, metadata)] * B
+        # run(Q [B, D], k) -> [(indices, scores, metadata)] * B; filtered batches: run(Q, k, filters)
+        self._run = run
         self._max = max_batch
         self._inflight = max(1, int(max_inflight))
         # adaptive linger: callers come back in waves (each waits for its own result), so a leader
@@ -172,8 +197,8 @@ class _QueryCoalescer:
     def _kclass(k: int) -> int:
         return 0 if k <= 16 else 1 if k <= 200 else 2
 
-    def query(self, q: np.ndarray, k: int):
-        req = [q, int(k), None, None]  # query, k, result, error
+    def query(self, q: np.ndarray, k: int, filt=None):
+        req = [q, int(k), None, None, filt]  # query, k, result, error, filter (None: unfiltered)
         self._cv.acquire()
         try:
             self._pending.append(req)
@@ -195,15 +220,18 @@ class _QueryCoalescer:
                         self._cv.wait(rem)
                     continue  # (another leader may have taken the requests meanwhile)
                 kc = self._kclass(self._pending[0][1])
+                fk = self._pending[0][4] is not None  # ... and its kind: filtered or not
                 batch, rest = [], []
                 for r in self._pending:
-                    (batch if len(batch) < self._max and self._kclass(r[1]) == kc else rest).append(r)
+                    (batch if len(batch) < self._max and self._kclass(r[1]) == kc and (r[4] is not None) == fk
+                     else rest).append(r)
                 self._pending = rest
                 self._running += 1
                 self._cv.release()
                 try:
                     kmax = max(r[1] for r in batch)
-                    res = self._run(np.stack([r[0] for r in batch]), kmax)
+                    Q = np.stack([r[0] for r in batch])
+                    res = self._run(Q, kmax, [r[4] for r in batch]) if fk else self._run(Q, kmax)
                     for r, (ix, sc, md) in zip(batch, res):
                         r[2] = (ix[:r[1]], sc[:r[1]], md[:r[1]])
                 except BaseException as e:  # every caller of the batch sees the failure
@@ -241,7 +269,8 @@ class MLXVectorStore:
         self._vector_count = 0
         self._hnsw_index = None
         self._files = StoreFiles(self.store_path)
-        self._coalescer = _QueryCoalescer(lambda Q, k: self._brute_force_search(Q, k, None),
+        self._coalescer = _QueryCoalescer(lambda Q, k, filters=None: self._search_filtered(
+                                              Q, k, filters if filters is not None else [None] * Q.shape[0]),
                                           max_inflight=self.config.coalesce_inflight,
                                           linger_us=self.config.coalesce_linger_us)
         if self.config.enable_hnsw:  # service/optimized_vector_store.py:72-78
@@ -541,15 +570,22 @@ class MLXVectorStore:
                 except Exception as e:
                     logger.warning("HNSW-Suche fehlgeschlagen, falle auf Brute-Force zurück: %s", e)
             # k above the device limit is not coalesced: its error is the caller's alone
-            if (self.config.coalesce and not filter_metadata and self._compiled_similarity_fn
-                    and 0 < int(k) <= 1024):
+            if self.config.coalesce and self._compiled_similarity_fn and 0 < int(k) <= 1024:
                 if q.shape[0] != self._dim:
                     raise ValueError(f"Dimension mismatch: query has {q.shape[0]} dims, store holds {self._dim}")
-                return self._coalescer.query(q, k)
+                if not filter_metadata:
+                    return self._coalescer.query(q, k)
+                # a filter the planner searches as a row list joins a batch of such filters (one
+                # device call for all of them); any other keeps its own masked search
+                eligible = self._meta_index.bitmap(filter_metadata, self._vector_count)[1]
+                if eligible == 0:
+                    return [], [], []
+                if self._subset_ok(eligible):
+                    return self._coalescer.query(q, k, filter_metadata)
             return self._brute_force_search(q[None, :], k, filter_metadata)[0]
 
     def batch_query(self, query_vectors: Union[np.ndarray, Any], k: int = 10,
-                    filter_metadata: Optional[Dict] = None) -> List[Tuple]:
+                    filter_metadata: Optional[Union[Dict, List[Optional[Dict]]]] = None) -> List[Tuple]:
         """The batched path (performance/mlx_optimized.py:217-248) behind the store API that
         api/routes/vectors.py:291 and tests/demo.py:134-137 call: one (indices, distances,
         metadata) tuple per query, same rows and order as ``query`` for that vector.
@@ -558,51 +594,103 @@ class MLXVectorStore:
         /vectors/batch_query unpacks ``indices, distances, metadata_list`` and scores cosine
         as ``max(0, 1.0 - dist)`` and euclidean as ``1 / (1 + dist)``
         (api/routes/vectors.py:300-306).  So cosine returns ``1 - cos`` and euclidean the
-        sqrt-L2 distance (which is what ``query`` already returns for euclidean)."""
+        sqrt-L2 distance (which is what ``query`` already returns for euclidean).
+
+        ``filter_metadata``: one dict for every query, or a list of B dicts / Nones, one filter
+        per query (the reference's multi-tenant use: each request its own user / model filter)."""
         q = _as_matrix(query_vectors)
         if q.ndim == 1:
             q = q[None, :]
         if q.ndim != 2:
             raise ValueError(f"query_vectors must be 2-D (B, dim), got {q.shape}")
+        per_query = isinstance(filter_metadata, (list, tuple))
+        if per_query and len(filter_metadata) != q.shape[0]:
+            raise ValueError(f"{q.shape[0]} queries but {len(filter_metadata)} filters")
         with _Read(self._rw):
             if self._vector_count == 0 or q.shape[0] == 0:
                 return [([], [], []) for _ in range(q.shape[0])]
-            res = self._brute_force_search(q, k, filter_metadata)
+            if per_query:
+                res = self._search_filtered(q, k, list(filter_metadata))
+            else:
+                res = self._brute_force_search(q, k, filter_metadata)
         if self.config.metric == "cosine":
             res = [(i, [1.0 - s for s in sc], m) for i, sc, m in res]
         return res
 
     def _brute_force_search(self, Q: np.ndarray, k: int, filter_metadata: Optional[Dict] = None):
         """service/optimized_vector_store.py:149-192 for a [B, D] block of queries
-        (called with the read lock held)."""
+        (called with the read lock held): the planner with one filter for every query."""
+        return self._search_filtered(Q, k, [filter_metadata] * Q.shape[0])
+
+    def _subset_ok(self, eligible: int) -> bool:
+        """A filter with ``eligible`` matching rows is searched as a row list (the planner's rule)."""
+        frac = float(self.config.subset_max_fraction)
+        return (frac > 0.0 and len(self._devices()) == 1 and hasattr(self._index, "search_rows")
+                and eligible <= frac * self._vector_count)
+
+    def _search_filtered(self, Q: np.ndarray, k: int, filters: List[Optional[Dict]]):
+        """The planner of every brute-force read (called with the read lock held): ``filters``
+        holds one entry per query, a dict or None.  Queries are grouped by filter.  A group without
+        a filter, one whose eligible rows exceed ``subset_max_fraction`` of the store and any group
+        on a multi-device store take one ``search`` each (row_mask = the filter's bitmap); all
+        other groups go into ONE ``search_rows`` call, one row list per distinct filter.  Both
+        device paths rank by the same exact keys, so the choice never shows in the results."""
         if not self._compiled_similarity_fn:
             raise RuntimeError(_NO_OPERATOR_MSG)
         B = Q.shape[0]
-        empty = [([], [], []) for _ in range(B)]
         if Q.shape[1] != self._dim:
             raise ValueError(f"Dimension mismatch: query has {Q.shape[1]} dims, store holds {self._dim}")
+        if len(filters) != B:
+            raise ValueError(f"{B} queries but {len(filters)} filters")
         k = int(k)
         if k <= 0:
-            return empty
+            return [([], [], []) for _ in range(B)]
         n = self._vector_count
-        mask = None
-        eligible = n
-        if filter_metadata:
+        out: List[Optional[Tuple]] = [None] * B
+        groups: Dict[Any, Tuple[Optional[Dict], List[int]]] = {}
+        for b, f in enumerate(filters):
+            groups.setdefault(_filter_key(f) if f else None, (f if f else None, []))[1].append(b)
+        masked, subset = [], []
+        for filt, members in groups.values():
+            if filt is None:
+                masked.append((None, n, members))
+                continue
             # posting lists maintained at add time, not the reference's O(N) scan (:159-165)
-            mask, eligible = self._meta_index.bitmap(filter_metadata, n)
+            mask, eligible = self._meta_index.bitmap(filt, n)
             if eligible == 0:
-                return empty
-        kk = min(k, eligible)
-        if kk > 1024:
-            raise ValueError(f"k={k} exceeds the device top-k limit of 1024")
-        scores, idx = self._index.search(Q, kk, row_mask=mask)
-        out = []
-        meta = self._metadata
-        for b in range(B):
-            valid = idx[b] >= 0
-            ib = idx[b][valid].tolist()
-            sb = scores[b][valid].astype(np.float64).tolist()
-            out.append((ib, sb, [meta[i] if i < len(meta) else {} for i in ib]))
+                for b in members:
+                    out[b] = ([], [], [])
+            elif self._subset_ok(eligible):
+                subset.append((filt, eligible, members))
+            else:
+                masked.append((mask, eligible, members))
+
+        def fill(members, scores, idx):
+            meta = self._metadata
+            for j, b in enumerate(members):
+                valid = idx[j] >= 0
+                ib = idx[j][valid].tolist()
+                sb = scores[j][valid].astype(np.float64).tolist()
+                out[b] = (ib, sb, [meta[i] if i < len(meta) else {} for i in ib])
+
+        def take(members):
+            return Q if members == list(range(B)) else Q[members]  # (one group: Q as it is)
+
+        for mask, eligible, members in masked:
+            kk = min(k, eligible)
+            if kk > 1024:
+                raise ValueError(f"k={k} exceeds the device top-k limit of 1024")
+            scores, idx = self._index.search(take(members), kk, row_mask=mask)
+            fill(members, scores, idx)
+        if subset:
+            kk = min(k, max(e for _, e, _ in subset))  # (a shorter list pads its rows with -1)
+            if kk > 1024:
+                raise ValueError(f"k={k} exceeds the device top-k limit of 1024")
+            members = [b for _, _, mem in subset for b in mem]
+            lists = [self._meta_index.rows(filt, n) for filt, _, _ in subset]
+            qlist = np.concatenate([np.full(len(mem), li, np.int32) for li, (_, _, mem) in enumerate(subset)])
+            scores, idx = self._index.search_rows(take(members), kk, lists, query_list=qlist)
+            fill(members, scores, idx)
         return out
 
     # ---- misc API ----------------------------------------------------------------------
