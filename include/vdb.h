@@ -148,7 +148,8 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "dir_bound" (0: BF16 certificate with |q| R only), "remove_chunk" / "update_chunk" (rows per
  * chunk of vdb_index_remove's scratch / vdb_index_update's staging, 0 = by bytes), "subset_wgs"
  * (workgroups per query of vdb_index_search_rows, 0 = auto; its stats "subset_searches",
- * "subset_queries", "subset_rows", "subset_bad_ids" are described there).  Stats also: "searches", "queries",
+ * "subset_queries", "subset_rows", "subset_bad_ids" are described there; vdb_index_search_range's
+ * are "range_searches", "range_queries").  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -276,6 +277,52 @@ int32_t vdb_index_search_rows(vdb_index* idx, const float* queries, int32_t n_qu
                               const int32_t* query_list, int32_t mem,
                               float* out_scores, int64_t* out_indices, double* out_keys,
                               int64_t index_offset, void* stream);
+
+/* Range search: every stored row within a score threshold of a query, exactly, with exact counts.
+ * Replaces: the "ask for more and cut" the reference's own RAG pipeline does, a k * 2 fetch with
+ * the results under min_similarity dropped afterwards (integrations/mlx_lm_pipeline.py:725-736),
+ * which silently returns too few whenever more than 2k rows qualify; and it answers what no top-k
+ * call can: "is anything within t of this vector" and "how many rows are within t".
+ *   thresholds   [n_queries] fp64, in score units.  cosine: a minimum similarity t, kt = t.
+ *                euclidean: a radius t >= 0, kt = -(t * t) (one fp64 multiply).  -inf (cosine) or
+ *                +inf (euclidean) passes every eligible row.
+ *   row_mask     as vdb_index_search.
+ *   cap          slots per query, >= 0, with n_queries * cap <= 2^36 (else VDB_ERR_INVALID, for
+ *                either memory kind).  0 = count only (the three list pointers may be NULL).
+ *   out_counts   [n_queries] int64, required: the exact number of eligible passing rows, also
+ *                when it exceeds cap.
+ *   out_indices  [n_queries, cap] int64, out_scores [n_queries, cap] fp32 (required when cap > 0),
+ *   out_keys     NULL or [n_queries, cap] fp64.
+ *   queries, mem, index_offset, stream: as vdb_index_search; all pointers of one memory kind.
+ *                n_queries == 0 is VDB_OK.  index_offset is added to the returned ids only.
+ * Result: row r passes query b when its canonical fp64 key -- the key vdb_index_search ranks by
+ * and returns in out_keys -- satisfies key >= kt[b]; a key equal to kt passes.  The first
+ * min(count, cap) passing rows are returned in ASCENDING ROW ID, each with its key rounded to the
+ * fp32 score as a search rounds it; the slots after them hold index -1 / score 0 / key -inf, and
+ * nothing at or past cap is written.  (Ascending row order needs no sort of unbounded length and
+ * never depends on the order atomics land in; best-first for a result that fits is one host sort,
+ * and best-first truncated is what vdb_index_search is.)  The result is the same bytes for every
+ * precision setting: the rows come from the row-major fp32 copy, the candidate copies are not
+ * read and no "searches_*" stat moves.
+ * Launches, per block of up to 64 queries (fewer for long rows): a scan that reads every row once
+ * for the whole block and writes a hit bitmap per query plus per-workgroup hit counts (no
+ * atomics); a prefix over those counts, which also gives the exact totals; and, when cap > 0, an
+ * emit that writes the ids of the hits below cap and a scoring pass over the filled slots, so the
+ * list work is proportional to min(count, cap).  Blocks run one after another on one stream over
+ * the same scratch.
+ * Host-memory calls are validated before anything is launched: NaN / Inf in a query ->
+ * VDB_ERR_NONFINITE; a NaN threshold, a negative euclidean radius or a cap outside its bounds ->
+ * VDB_ERR_INVALID.  A device-memory call cannot be validated without a sync (the cap aside): its kernel gives a
+ * query with a NaN threshold or a negative radius a count of 0, and nothing out of bounds is read
+ * or written.  Device-memory calls are stream-ordered and read nothing back; host-memory calls
+ * take a per-search workspace, its stream and one pinned staging copy each way, as
+ * vdb_index_search_rows does.  Takes the index's shared lock (add / remove / update / clear wait
+ * for queued calls).  An empty index gives counts 0 and every slot "no result".  Stats
+ * (cumulative, successful calls): "range_searches", "range_queries". */
+int32_t vdb_index_search_range(vdb_index* idx, const float* queries, int32_t n_queries,
+                               const double* thresholds, const uint32_t* row_mask, int32_t mem,
+                               int64_t cap, int64_t* out_counts, int64_t* out_indices,
+                               float* out_scores, double* out_keys, int64_t index_offset, void* stream);
 
 /* --- multi-GPU merge -----------------------------------------------------------
  * Merge per-shard top-k lists (all device memory, already all-gathered):

@@ -70,6 +70,17 @@ class VectorQuery(BaseModel):
     filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
 
 
+class VectorRangeQuery(BaseModel):
+    """Every stored row within ``threshold`` of the query: a minimum similarity for a cosine
+    store, a maximum distance for a euclidean one."""
+    user_id: str
+    model_id: str
+    query: List[float] = Field(..., description="Query vector")
+    threshold: float = Field(..., description="Minimum similarity (cosine) / maximum distance (euclidean)")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    limit: int = Field(default=1000, ge=1, le=100000, description="Most results returned (the best ones)")
+
+
 class BatchQueryRequest(BaseModel):
     user_id: str
     model_id: str
@@ -116,6 +127,13 @@ class VectorAddResponse(BaseModel):
 
 class VectorQueryResponse(BaseModel):
     results: List[Dict[str, Any]]
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorRangeQueryResponse(BaseModel):
+    results: List[Dict[str, Any]]
+    total_matches: int  # the exact number of rows within the threshold; may exceed len(results)
     query_time_ms: float
     total_vectors_searched: int
 
@@ -285,6 +303,37 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:  # the reference turns every error, its own 400s included, into a 500
             logger.error("Error querying vectors: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Query failed: {e}")
+
+    @router.post("/range_query", response_model=VectorRangeQueryResponse)
+    async def range_query_vectors(request: VectorRangeQuery, api_key: str = Depends(auth)):
+        """Every row within the threshold, best first, at most ``limit`` of them; ``total_matches``
+        is the exact count.  A bad request (empty query, NaN threshold, negative radius, dimension
+        mismatch: the store's ValueError) is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if not request.query:
+                raise HTTPException(status_code=400, detail="Query vector required")
+
+            # the best `limit` hits and the exact total from one device call: no more than `limit`
+            # result entries are ever built
+            loop = asyncio.get_running_loop()
+            indices, scores, metas, total = await loop.run_in_executor(
+                mgr._executor, lambda: store.range_query(request.query, request.threshold,
+                                                         filter_metadata=request.filter_metadata,
+                                                         limit=request.limit, with_total=True))
+            return VectorRangeQueryResponse(results=format_query_results(store.config.metric, indices, scores, metas),
+                                            total_matches=total, query_time_ms=(time.time() - t0) * 1000,
+                                            total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Range query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Range query failed: {e}")
+        except Exception as e:
+            logger.error("Error in range query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Range query failed: {e}")
 
     @router.post("/batch_query", response_model=BatchQueryResponse)
     async def batch_query_vectors(request: BatchQueryRequest, api_key: str = Depends(auth)):

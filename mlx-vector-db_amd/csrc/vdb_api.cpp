@@ -24,6 +24,7 @@
 #include "../../include/vdb.h"
 #include "vdb_compact_plan.h"
 #include "vdb_subset_plan.h"
+#include "vdb_range_plan.h"
 #include "vdb_internal.h"
 
 using namespace vdb;
@@ -230,6 +231,7 @@ struct vdb_index {
     // device-memory call's kernel skipped are counted on the device (d_xmax + kSubsetBadWord)
     std::atomic<int64_t> n_subset_searches{0}, n_subset_queries{0}, n_subset_rows{0};
     int64_t subset_wgs = 0;  // knob: workgroups per query of a row-list search (0 = auto)
+    std::atomic<int64_t> n_range_searches{0}, n_range_queries{0};  // vdb_index_search_range (successful calls)
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -1021,6 +1023,8 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "subset_searches") *value = ix->n_subset_searches.load();
     else if (n == "subset_queries") *value = ix->n_subset_queries.load();
     else if (n == "subset_rows") *value = ix->n_subset_rows.load();
+    else if (n == "range_searches") *value = ix->n_range_searches.load();
+    else if (n == "range_queries") *value = ix->n_range_queries.load();
     else if (n == "subset_bad_ids") {  // counted by the kernel: after the row-list searches queued so far
         HIP_TRY(hipSetDevice(ix->device));
         const int wr = wait_idle(ix);
@@ -2471,6 +2475,126 @@ int32_t vdb_index_search_rows(vdb_index* ix, const float* queries, int32_t B, in
     ix->n_subset_searches++;
     ix->n_subset_queries += B;
     ix->n_subset_rows += n_ids;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_range(vdb_index* ix, const float* queries, int32_t B, const double* thresholds,
+                               const uint32_t* row_mask, int32_t mem, int64_t cap, int64_t* out_counts,
+                               int64_t* out_indices, float* out_scores, double* out_keys, int64_t index_offset,
+                               void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (B == 0) return VDB_OK;
+    if (B < 0) return set_error(VDB_ERR_INVALID, "n_queries must be >= 0, got %d", B);
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    if (range_validate_cap(B, cap))
+        return set_error(VDB_ERR_INVALID, "cap must be >= 0 and n_queries * cap <= %lld, got cap %lld for %d queries",
+                         (long long)kRangeMaxSlots, (long long)cap, B);
+    if (!queries || !thresholds || !out_counts) return set_error(VDB_ERR_INVALID, "NULL query/threshold/count pointer");
+    if (cap > 0 && (!out_indices || !out_scores))
+        return set_error(VDB_ERR_INVALID, "out_indices and out_scores are required when cap > 0");
+    const int D = ix->dim;
+    const bool host = mem == VDB_MEM_HOST;
+    if (host) {  // everything checked before any launch
+        if (!all_finite(queries, (int64_t)B * D)) return set_error(VDB_ERR_NONFINITE, "query contains NaN or Inf");
+        int64_t at = 0;
+        switch (range_validate(ix->metric, thresholds, B, &at)) {
+            case kRangeNanThreshold: return set_error(VDB_ERR_INVALID, "thresholds[%lld] is NaN", (long long)at);
+            case kRangeNegRadius:
+                return set_error(VDB_ERR_INVALID, "thresholds[%lld] = %g: a euclidean radius must be >= 0", (long long)at,
+                                 thresholds[at]);
+            default: break;
+        }
+    }
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // as vdb_index_search_rows: the caller's stream (device memory: NULL = the null stream), or for
+    // a host-memory call without one the stream of the workspace it takes
+    const bool own_stream = host && !stream;
+    hipStream_t st = own_stream ? nullptr : (hipStream_t)stream;
+    Workspace* w = acquire_ws(ix, st, own_stream);
+    if (own_stream) {
+        if (!w->own) {
+            const hipError_t e = hipStreamCreateWithFlags(&w->own, hipStreamNonBlocking);
+            if (e != hipSuccess) {
+                std::lock_guard<std::mutex> lg(ix->ws_mu);
+                w->busy = false;
+                return set_error(VDB_ERR_HIP, "workspace stream: %s", hipGetErrorString(e));
+            }
+        }
+        st = w->own;
+    }
+    struct Releaser {
+        vdb_index* ix; Workspace* w; hipStream_t st;
+        ~Releaser() { release_ws(ix, w, st); }
+    } rel{ix, w, st};
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const RangeScratch sc = range_scratch(B, D, ix->Dp, N, cap, host, masked, out_keys != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    RangeArgs a{};
+    a.Q = queries;
+    a.thr = thresholds;
+    a.mask = masked ? row_mask : nullptr;
+    a.out_c = out_counts;
+    a.out_i = out_indices;
+    a.out_s = out_scores;
+    a.out_k = out_keys;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = ws_host_io(w, (size_t)(sc.in_bytes + sc.out_bytes));
+        if (rc) return rc;
+        char* h = w->host_io;
+        std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+        std::memcpy(h + (sc.thr - sc.in0), thresholds, (size_t)B * 8);
+        if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.n_words * 4);
+        HIP_TRY(hipMemcpyAsync(dev + sc.in0, h, (size_t)sc.in_bytes, hipMemcpyHostToDevice, st));
+        a.Q = reinterpret_cast<const float*>(dev + sc.q);
+        a.thr = reinterpret_cast<const double*>(dev + sc.thr);
+        a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.out_c = reinterpret_cast<int64_t*>(dev + sc.out_c);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        a.out_k = out_keys ? reinterpret_cast<double*>(dev + sc.out_k) : nullptr;
+    }
+    if (cap == 0) a.out_i = nullptr, a.out_s = nullptr, a.out_k = nullptr;
+    if (N == 0) {  // an empty index: counts 0 and every slot "no result"
+        HIP_TRY(hipMemsetAsync(a.out_c, 0, (size_t)B * 8, st));
+        if (cap > 0) HIP_TRY(launch_empty_results((int64_t)B * cap, a.out_s, a.out_i, a.out_k, st));
+    } else {
+        double* qn64 = reinterpret_cast<double*>(dev + sc.qn64);
+        // the canonical query norms, nothing else: no query tiles
+        HIP_TRY(launch_prep_queries(a.Q, B, B, D, ix->G, ix->metric, nullptr, nullptr, qn64, nullptr, nullptr, nullptr,
+                                    nullptr, nullptr, st));
+        a.qn64 = qn64;
+        a.X = ix->X;
+        a.G = ix->G;
+        a.D = D;
+        a.nrm64 = ix->nrm64;
+        a.N = N;
+        a.H = reinterpret_cast<uint32_t*>(dev + sc.H);
+        a.part = reinterpret_cast<uint32_t*>(dev + sc.part);
+        a.cnt = reinterpret_cast<int64_t*>(dev + sc.cnt);
+        a.cap = cap;
+        a.index_offset = index_offset;
+        // block after block on this stream over the same scratch
+        for (int b0 = 0; b0 < B; b0 += sc.block)
+            HIP_TRY(launch_range_block(ix->metric, a, b0, std::min(sc.block, B - b0), st));
+    }
+    if (host) {
+        char* r = w->host_io + sc.in_bytes;
+        HIP_TRY(hipMemcpyAsync(r, dev + sc.out0, (size_t)sc.out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::memcpy(out_counts, r + (sc.out_c - sc.out0), (size_t)B * 8);
+        if (cap > 0) {
+            std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * cap * 8);
+            std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * cap * 4);
+            if (out_keys) std::memcpy(out_keys, r + (sc.out_k - sc.out0), (size_t)B * cap * 8);
+        }
+    }
+    ix->n_range_searches++;
+    ix->n_range_queries += B;
     return VDB_OK;
 }
 

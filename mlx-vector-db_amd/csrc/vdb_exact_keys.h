@@ -1,7 +1,8 @@
 // vdb_exact_keys.h: the exact fp64 key of a (query, row) pair, one wave per row, and its batched
 // forms (several rows' pieces in flight per wave).  Shared by the exact paths of vdb_exact.hip
-// (rerank, finish, exact scan) and the row-list search (vdb_subset.hip): every form accumulates in
-// the canonical order of vdb_common.h, so their keys are bit-identical.  Built with -ffp-contract=off.
+// (rerank, finish, exact scan), the row-list search (vdb_subset.hip) and the range search
+// (vdb_range.hip): every form accumulates in the canonical order of vdb_common.h, so their keys are
+// bit-identical.  Built with -ffp-contract=off.
 #pragma once
 #include "vdb_common.h"
 
@@ -107,6 +108,63 @@ __device__ __forceinline__ void exact_keys_rows(const float* __restrict__ q, int
     for (int u = 0; u < NB; ++u) {
         if (u < nb) out[u] = METRIC == 0 ? acc[u] / (fmax(qn, 1e-8) * fmax(xn[u], 1e-8)) : -acc[u];
     }
+}
+
+// The multi-query form of exact_keys_rows (the range scan, vdb_range.hip): the pieces of NB rows
+// are loaded once (rows_pieces_load; a row whose ok[u] is false is not read and holds zeros) and
+// then scored against one query after another (exact_keys_held), each key in the same canonical
+// order, so a block of queries costs one read of the rows.
+template <int NB, int MP>
+__device__ __forceinline__ void rows_pieces_load(const float* __restrict__ X, int G, int np, const uint32_t* rows,
+                                                 const bool* ok, f32x4 (&xv)[MP][NB]) {
+    const int lane = threadIdx.x & 63;
+    const int Dp = G * GROUP_DIMS;
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        const int p = m * 64 + lane;
+#pragma unroll
+        for (int u = 0; u < NB; ++u)
+            xv[m][u] = (m < np && ok[u] && 4 * p < Dp) ? *(const f32x4*)(X + row_piece_offset(rows[u], p, G))
+                                                       : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+template <int METRIC, int NB, int MP>
+__device__ __forceinline__ void exact_keys_held(const float* __restrict__ q, int D, double qn, int np,
+                                                const f32x4 (&xv)[MP][NB], const double* xn, double* out) {
+    const int lane = threadIdx.x & 63;
+    double acc[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) acc[u] = 0.0;
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        if (m < np) {
+            float qv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int d = 4 * (m * 64 + lane) + j;
+                qv[j] = d < D ? q[d] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < NB; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double qd = (double)qv[j];
+                    const double xd = (double)xv[m][u][j];
+                    if (METRIC == 0) {
+                        acc[u] = acc[u] + qd * xd;
+                    } else {
+                        const double df = xd - qd;
+                        acc[u] = acc[u] + df * df;
+                    }
+                }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int u = 0; u < NB; ++u) acc[u] = acc[u] + __shfl_xor(acc[u], off, 64);
+#pragma unroll
+    for (int u = 0; u < NB; ++u) out[u] = METRIC == 0 ? acc[u] / (fmax(qn, 1e-8) * fmax(xn[u], 1e-8)) : -acc[u];
 }
 
 // ... and for rows of any length: one piece of each of the NB rows in flight per trip.

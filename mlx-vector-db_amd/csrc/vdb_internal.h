@@ -353,6 +353,22 @@ struct SubsetArgs {
 size_t subset_lds_bytes(int KE, int n_seg);
 hipError_t launch_subset_search(int metric, const SubsetArgs& a, int n_queries, int n_seg, hipStream_t st);
 
+// Range search (vdb_range.hip, vdb_index_search_range): queries [b0, b0 + qb) of the batch (qb at
+// most kRangeMaxBlock, vdb_range_plan.h) against rows [0, N), N >= 1.  Row r passes query b when
+// its canonical fp64 key is at or above range_kt(metric, thr[b]) and mask (optional, the row_mask
+// layout) has its bit.  out_c[b] = the exact number of passing rows; with cap > 0 the first
+// min(count, cap) of them in ascending row order go to out_i / out_s / out_k [b][cap] (out_k
+// optional) and the slots after them get "no result"; nothing at or past cap is written.  Four
+// launches (scan, prefix, emit, score; cap == 0: the first two) over the scratch H [qb][n_words],
+// part [qb][n_chunks], cnt [qb], which the next block of the same stream reuses.
+struct RangeArgs {
+    const float* Q; const double* thr; const double* qn64; const float* X; int G; int D; const double* nrm64;
+    int64_t N; const uint32_t* mask;
+    uint32_t* H; uint32_t* part; int64_t* cnt;
+    int64_t cap; int64_t* out_c; int64_t* out_i; float* out_s; double* out_k; int64_t index_offset;
+};
+hipError_t launch_range_block(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st);
+
 // Merge sorted fp64-key lists.  Element (q, j, e) lives at q*sq + j*sj + e, lists
 // have Lk entries; output [nq][KP] sorted.
 hipError_t launch_merge_f64_u32(int KP, const double* lk, const uint32_t* li, int n_lists, int Lk,

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_set_param", "vdb_index_get_stat",
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
-    "vdb_index_search", "vdb_index_search_rows", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -103,6 +103,8 @@ def load_library():
             "vdb_index_search": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_index_search_rows": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp,
                                               c_vp, c_i64, c_vp]),
+            "vdb_index_search_range": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                               c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -401,6 +403,67 @@ class NativeIndex:
             ctypes.c_void_p(rows_ptr or None), int(n_ids), ctypes.c_void_p(query_list_ptr or None), MEM_DEVICE,
             ctypes.c_void_p(out_scores_ptr), ctypes.c_void_p(out_idx_ptr), ctypes.c_void_p(out_keys_ptr or None),
             int(index_offset), ctypes.c_void_p(stream or None)))
+
+    # largest capacity a ``search_range`` call without a ``cap`` starts with
+    RANGE_FIRST_CAP = 1024
+
+    def search_range(self, queries: np.ndarray, thresholds, cap: Optional[int] = None,
+                     row_mask: Optional[np.ndarray] = None, with_keys: bool = False, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_range, host memory: every row whose exact key is at or
+        above the query's threshold (cosine: similarity >= t; euclidean: distance <= t), in
+        ascending row id.  ``thresholds``: one fp64 per query, or a scalar for all of them.
+        Returns (counts i64 [B], indices i64 [B, cap], scores f32 [B, cap][, keys f64 [B, cap]]):
+        counts are exact even above ``cap``; slots past min(count, cap) are -1 / 0 / -inf.
+        ``cap=0`` counts only.  ``cap=None``: every hit is returned -- a call with cap 1024 and,
+        if a count exceeds it, one more with cap = the largest count."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must have shape (B, {self.dim}), got {np.shape(queries)}")
+        B = q.shape[0]
+        thr = np.asarray(thresholds, dtype=np.float64)
+        if thr.ndim == 0:
+            thr = np.full(B, float(thr), dtype=np.float64)
+        thr = np.ascontiguousarray(thr.reshape(-1))
+        if thr.size != B:
+            raise ValueError(f"thresholds needs {B} entries, got {thr.size}")
+        mask_p = None
+        if row_mask is not None:
+            m = np.ascontiguousarray(row_mask, dtype=np.uint32)
+            need = (self.count() + 31) // 32
+            if m.size < need:
+                raise ValueError(f"row_mask needs {need} uint32 words, got {m.size}")
+            mask_p = _ptr(m)
+
+        def call(c):
+            counts = np.zeros(B, dtype=np.int64)
+            idx = np.empty((B, max(c, 0)), dtype=np.int64)  # (a negative cap is the library's to refuse)
+            scores = np.empty((B, max(c, 0)), dtype=np.float32)
+            keys = np.empty((B, max(c, 0)), dtype=np.float64) if with_keys else None
+            _check(self._lib.vdb_index_search_range(
+                self._h, _ptr(q), B, _ptr(thr), mask_p, MEM_HOST, c, _ptr(counts), _ptr(idx) if c > 0 else None,
+                _ptr(scores) if c > 0 else None, _ptr(keys) if keys is not None and c > 0 else None,
+                int(index_offset), None))
+            return (counts, idx, scores, keys) if with_keys else (counts, idx, scores)
+
+        if cap is not None:
+            return call(int(cap))
+        out = call(self.RANGE_FIRST_CAP)
+        most = int(out[0].max()) if B else 0
+        return call(most) if most > self.RANGE_FIRST_CAP else out
+
+    def search_range_device(self, q_ptr: int, n_queries: int, thresholds_ptr: int, cap: int, out_counts_ptr: int,
+                            out_idx_ptr: int = 0, out_scores_ptr: int = 0, out_keys_ptr: int = 0, mask_ptr: int = 0,
+                            index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_range with device-memory arguments (fp32 queries, fp64 thresholds,
+        int64 counts and indices); stream-ordered, nothing is read back and the thresholds are not
+        validated on the host (include/vdb.h)."""
+        _check(self._lib.vdb_index_search_range(
+            self._h, ctypes.c_void_p(q_ptr), int(n_queries), ctypes.c_void_p(thresholds_ptr),
+            ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, int(cap), ctypes.c_void_p(out_counts_ptr),
+            ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_scores_ptr or None),
+            ctypes.c_void_p(out_keys_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
 
 
 class NativeShards:

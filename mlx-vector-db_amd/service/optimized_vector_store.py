@@ -693,6 +693,99 @@ class MLXVectorStore:
             fill(members, scores, idx)
         return out
 
+    # ---- range query ----------------------------------------------------------------
+    def range_query(self, query_vector: Union[np.ndarray, Any], threshold: float,
+                    filter_metadata: Optional[Dict] = None, limit: Optional[int] = None,
+                    with_total: bool = False) -> Tuple:
+        """Every stored row within ``threshold`` of the query -> (indices, scores, metadata), best
+        first: cosine rows with similarity >= threshold, score descending; euclidean rows with
+        distance <= threshold, distance ascending; ties to the lower row, the order ``query``
+        uses, and the scores ``query`` returns.  ``limit`` keeps the best ``limit`` after sorting.
+        Exact (include/vdb.h vdb_index_search_range), and not capped at 1024 results as ``query``
+        is.  The reference has no such read: its RAG pipeline fetches k * 2 and drops what is under
+        min_similarity (integrations/mlx_lm_pipeline.py:725-736).  ``with_total``: a fourth element,
+        the exact number of rows within the threshold (what ``count_within`` returns), from the
+        same device call: with a ``limit`` only the best ``limit`` entries are built."""
+        q = _as_matrix(query_vector)
+        if q.ndim == 2 and q.shape[0] == 1:
+            q = q[0]
+        if q.ndim != 1:
+            raise ValueError(f"range_query takes one vector of shape (dim,) or (1, dim), got {q.shape}; "
+                             "use batch_range_query for several")
+        res = self._range_search(q[None, :], [threshold], filter_metadata, limit)[0]
+        return res if with_total else res[:3]
+
+    def batch_range_query(self, query_vectors: Union[np.ndarray, Any], thresholds,
+                          filter_metadata: Optional[Dict] = None) -> List[Tuple]:
+        """``range_query`` for a [B, dim] block of queries from one device call: one (indices,
+        scores, metadata) tuple per query.  ``thresholds``: one per query, or a scalar for all."""
+        q = _as_matrix(query_vectors)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError(f"query_vectors must be 2-D (B, dim), got {q.shape}")
+        thr = np.asarray(thresholds, dtype=np.float64)
+        thr = np.full(q.shape[0], float(thr)) if thr.ndim == 0 else thr.reshape(-1)
+        if thr.size != q.shape[0]:
+            raise ValueError(f"{q.shape[0]} queries but {thr.size} thresholds")
+        return [r[:3] for r in self._range_search(q, thr, filter_metadata, None)]
+
+    def count_within(self, query_vector: Union[np.ndarray, Any], threshold: float,
+                     filter_metadata: Optional[Dict] = None) -> int:
+        """How many stored rows ``range_query`` would return, from a count-only device call."""
+        q = _as_matrix(query_vector)
+        if q.ndim == 2 and q.shape[0] == 1:
+            q = q[0]
+        if q.ndim != 1:
+            raise ValueError(f"count_within takes one vector of shape (dim,) or (1, dim), got {q.shape}")
+        self._check_can_range()
+        with _Read(self._rw):
+            mask = self._range_mask(q[None, :], filter_metadata)
+            if mask is False:
+                return 0
+            return int(self._index.search_range(q[None, :], [float(threshold)], cap=0, row_mask=mask)[0][0])
+
+    def _check_can_range(self):
+        if len(self._devices()) > 1:
+            raise NotImplementedError("range query is not supported on a multi-device store")
+
+    def _range_mask(self, Q: np.ndarray, filter_metadata: Optional[Dict]):
+        """The row_mask of a range read (read lock held): None without a filter, False when the
+        store is empty or nothing matches the filter (no device call is needed)."""
+        if self._vector_count == 0:
+            return False
+        if not self._compiled_similarity_fn:
+            raise RuntimeError(_NO_OPERATOR_MSG)
+        if Q.shape[1] != self._dim:
+            raise ValueError(f"Dimension mismatch: query has {Q.shape[1]} dims, store holds {self._dim}")
+        if not filter_metadata:
+            return None
+        mask, eligible = self._meta_index.bitmap(filter_metadata, self._vector_count)
+        return mask if eligible else False
+
+    def _range_search(self, Q: np.ndarray, thresholds, filter_metadata: Optional[Dict], limit: Optional[int]):
+        """One (indices, scores, metadata, total) tuple per query; total = the exact hit count."""
+        self._check_can_range()
+        if limit is not None and int(limit) < 0:
+            raise ValueError(f"limit must be >= 0, got {limit}")
+        with _Read(self._rw):
+            mask = self._range_mask(Q, filter_metadata)
+            if mask is False:
+                return [([], [], [], 0) for _ in range(Q.shape[0])]
+            thr = np.asarray(thresholds, dtype=np.float64)
+            counts, idx, scores, keys = self._index.search_range(Q, thr, row_mask=mask, with_keys=True)
+            meta = self._metadata
+            out = []
+            for b in range(Q.shape[0]):
+                n = int(counts[b])
+                order = np.lexsort((idx[b, :n], -keys[b, :n]))  # key descending, ties to the lower row
+                if limit is not None:
+                    order = order[:int(limit)]
+                ib = idx[b, :n][order].tolist()
+                sb = scores[b, :n][order].astype(np.float64).tolist()
+                out.append((ib, sb, [meta[i] if i < len(meta) else {} for i in ib], n))
+            return out
+
     # ---- misc API ----------------------------------------------------------------------
     def _warmup_kernels(self):
         """service/optimized_vector_store.py:194-196 (a no-op there); here: one tiny search."""
