@@ -149,7 +149,10 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * chunk of vdb_index_remove's scratch / vdb_index_update's staging, 0 = by bytes), "subset_wgs"
  * (workgroups per query of vdb_index_search_rows, 0 = auto; its stats "subset_searches",
  * "subset_queries", "subset_rows", "subset_bad_ids" are described there; vdb_index_search_range's
- * are "range_searches", "range_queries").  Stats also: "searches", "queries",
+ * are "range_searches", "range_queries"), "group_fetch" (rows vdb_index_search_groups' inner
+ * search fetches, 0 = auto, 1..200) and "group_force_exact" (0/1; its stats "group_rows",
+ * "group_sets", "group_searches", "group_queries", "group_fallback_queries" are described
+ * there).  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -323,6 +326,58 @@ int32_t vdb_index_search_range(vdb_index* idx, const float* queries, int32_t n_q
                                const double* thresholds, const uint32_t* row_mask, int32_t mem,
                                int64_t cap, int64_t* out_counts, int64_t* out_indices,
                                float* out_scores, double* out_keys, int64_t index_offset, void* stream);
+
+/* Grouped search: the k best DISTINCT groups of a query, each with its best row (Qdrant's "search
+ * groups", Milvus' "group by").
+ * Replaces: nothing in the reference's store; its RAG pipeline stores document_id /
+ * document_source beside every chunk (integrations/mlx_lm_pipeline.py:656-670, :747-751) and can
+ * only ask for the best k chunks.  Without this call: over-fetch with vdb_index_search and
+ * de-duplicate on the host, which returns too few documents whenever one long document fills the
+ * fetched list.
+ *
+ * vdb_index_set_groups attaches a group column: groups [n] int32, n == count (else
+ * VDB_ERR_INVALID), host or device memory per `mem` (device: read after the work queued on
+ * `stream`).  A negative id means the row has no group and is never returned.  The index keeps a
+ * device copy, builds the bitmap of the rows with an id >= 0 and notes whether any id is negative.
+ * groups == NULL with n == 0 detaches the column.  Takes the exclusive lock, waits for queued
+ * searches and returns when done, as an add does.  Every successful add, remove and clear drops
+ * the column (its rows no longer line up); vdb_index_update keeps it.  Stats: "group_rows" (rows
+ * attached, 0 = none), "group_sets" (cumulative).
+ *
+ * vdb_index_search_groups:
+ *   k            1..128 groups per query
+ *   out_groups   [n_queries, k] int32, required: the group id of each slot, -1 = no result
+ *   out_scores / out_indices / out_keys: [n_queries, k], slot j = the BEST ROW of the j-th group
+ *   queries, row_mask, mem, index_offset, stream: as vdb_index_search; all pointers of one memory
+ *                kind.  n_queries == 0 is VDB_OK; at most 65 535 queries per call.
+ * Result: a row is eligible when its group id is >= 0 and row_mask (if given) has its bit.  The
+ * best row of a group is its eligible row with the best canonical fp64 key, ties to the lower row
+ * id (the order vdb_index_search uses); groups rank by (best key desc, best row asc).  The score
+ * is the key rounded to fp32 as a search rounds it.  Slots past the number of eligible groups
+ * hold index -1 / score 0 / key -inf / group -1.  The result is the same bytes for every
+ * precision setting and both memory kinds.
+ * How: the ordinary certified search fetches the best k' >= k eligible rows with their keys into
+ * scratch (k' <= 200; knob "group_fetch": 0 = auto, 200 rows, or 1 for k = 1; 1..200 sets it, never
+ * below k); one select kernel marks each group's first occurrence in that ranked list and writes
+ * the first k.  The list settles the query when it holds k groups, when it came back short of k',
+ * or when the call's eligible rows (those with a group and their mask bit, counted on the device;
+ * mask bits at or past count name no row) number at most k': then every eligible row was seen.
+ * Any other query is flagged on the device and answered by an exact scan kept per (key, row,
+ * group), launched for the whole batch and gated per query, so a device-memory call never waits.  Results are identical for every
+ * group_fetch; knob "group_force_exact" (0/1) sends every query to the exact scan (tests, A/B).
+ * Errors: no column attached, k outside [1, 128], n_queries above 65 535, a NULL queries / out_scores / out_indices /
+ * out_groups -> VDB_ERR_INVALID; host-memory queries with NaN / Inf -> VDB_ERR_NONFINITE, before
+ * anything is launched.  Device-memory calls are stream-ordered and read nothing back.  Takes the
+ * index's shared lock and a per-search workspace, as vdb_index_search_rows does.  An empty index
+ * (with an empty column attached) gives every slot "no result".  Stats (cumulative, successful
+ * calls): "group_searches", "group_queries", "group_fallback_queries" (counted on the device);
+ * "searches" / "queries" move once per call and the "searches_*" stats show the inner search's
+ * candidate pass. */
+int32_t vdb_index_set_groups(vdb_index* idx, const int32_t* groups, int64_t n, int32_t mem, void* stream);
+int32_t vdb_index_search_groups(vdb_index* idx, const float* queries, int32_t n_queries, int32_t k,
+                                const uint32_t* row_mask, int32_t mem,
+                                float* out_scores, int64_t* out_indices, int32_t* out_groups, double* out_keys,
+                                int64_t index_offset, void* stream);
 
 /* --- multi-GPU merge -----------------------------------------------------------
  * Merge per-shard top-k lists (all device memory, already all-gathered):

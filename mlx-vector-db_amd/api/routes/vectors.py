@@ -43,7 +43,7 @@ from fastapi import APIRouter, Depends, HTTPException, Security
 from fastapi.security import HTTPAuthorizationCredentials, HTTPBearer
 from pydantic import BaseModel, Field, model_validator
 
-from service.optimized_vector_store import MLXVectorStore, MLXVectorStoreConfig
+from service.optimized_vector_store import GROUP_MAX_K, GROUP_MAX_SIZE, MLXVectorStore, MLXVectorStoreConfig
 
 logger = logging.getLogger(__name__)
 
@@ -79,6 +79,18 @@ class VectorRangeQuery(BaseModel):
     threshold: float = Field(..., description="Minimum similarity (cosine) / maximum distance (euclidean)")
     filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
     limit: int = Field(default=1000, ge=1, le=100000, description="Most results returned (the best ones)")
+
+
+class VectorGroupQuery(BaseModel):
+    """The ``k`` best distinct values of the metadata key ``group_by`` (the best documents of a
+    chunked corpus), each with its best ``group_size`` rows."""
+    user_id: str
+    model_id: str
+    query: List[float] = Field(..., description="Query vector")
+    group_by: str = Field(..., description="Metadata key whose values are the groups")
+    k: int = Field(default=10, ge=1, le=GROUP_MAX_K, description="Groups returned")
+    group_size: int = Field(default=1, ge=1, le=GROUP_MAX_SIZE, description="Hits per group")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
 
 
 class BatchQueryRequest(BaseModel):
@@ -134,6 +146,13 @@ class VectorQueryResponse(BaseModel):
 class VectorRangeQueryResponse(BaseModel):
     results: List[Dict[str, Any]]
     total_matches: int  # the exact number of rows within the threshold; may exceed len(results)
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorGroupQueryResponse(BaseModel):
+    # best group first: {"group_value": ..., "hits": [{"metadata", "similarity_score", "rank"}, ...]}
+    groups: List[Dict[str, Any]]
     query_time_ms: float
     total_vectors_searched: int
 
@@ -334,6 +353,35 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in range query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Range query failed: {e}")
+
+    @router.post("/query_groups", response_model=VectorGroupQueryResponse)
+    async def query_groups_vectors(request: VectorGroupQuery, api_key: str = Depends(auth)):
+        """The ``k`` best groups (distinct values of ``group_by``), best first, each with its best
+        ``group_size`` hits.  A bad request (empty query, dimension mismatch: the store's
+        ValueError) is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if not request.query:
+                raise HTTPException(status_code=400, detail="Query vector required")
+            loop = asyncio.get_running_loop()
+            groups = await loop.run_in_executor(
+                mgr._executor, lambda: store.query_groups(request.query, request.group_by, k=request.k,
+                                                          group_size=request.group_size,
+                                                          filter_metadata=request.filter_metadata))
+            out = [{"group_value": g["group"], "hits": format_query_results(store.config.metric, *g["hits"])}
+                   for g in groups]
+            return VectorGroupQueryResponse(groups=out, query_time_ms=(time.time() - t0) * 1000,
+                                            total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Grouped query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Grouped query failed: {e}")
+        except Exception as e:
+            logger.error("Error in grouped query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Grouped query failed: {e}")
 
     @router.post("/batch_query", response_model=BatchQueryResponse)
     async def batch_query_vectors(request: BatchQueryRequest, api_key: str = Depends(auth)):

@@ -25,6 +25,7 @@
 #include "vdb_compact_plan.h"
 #include "vdb_subset_plan.h"
 #include "vdb_range_plan.h"
+#include "vdb_group_plan.h"
 #include "vdb_internal.h"
 
 using namespace vdb;
@@ -232,6 +233,20 @@ struct vdb_index {
     std::atomic<int64_t> n_subset_searches{0}, n_subset_queries{0}, n_subset_rows{0};
     int64_t subset_wgs = 0;  // knob: workgroups per query of a row-list search (0 = auto)
     std::atomic<int64_t> n_range_searches{0}, n_range_queries{0};  // vdb_index_search_range (successful calls)
+    // vdb_index_set_groups: the group column [group_n] (a device copy owned by the index), the bitmap
+    // of its rows with an id >= 0 (ceil(group_n / 32) words) and whether any id is negative; add,
+    // remove and clear drop it (group_set = false), update keeps it
+    int32_t* groups = nullptr;
+    uint32_t* group_valid = nullptr;
+    int64_t group_n = 0, group_cap = 0;
+    bool group_set = false, group_any_neg = false;
+    int64_t group_valid_rows = 0;  // rows with an id >= 0
+    // vdb_index_search_groups: calls and queries (successful calls), and the device's count of the
+    // queries that took the exact fallback
+    std::atomic<int64_t> n_group_sets{0}, n_group_searches{0}, n_group_queries{0};
+    unsigned long long* d_group_fb = nullptr;
+    int64_t group_fetch = 0;        // knob: rows the inner search fetches (0 = auto, vdb_group_plan.h)
+    int64_t group_force_exact = 0;  // knob: every query takes the exact fallback (tests, A/B)
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -794,6 +809,9 @@ int32_t vdb_index_destroy(vdb_index* ix) {
     if (ix->d_i8) (void)hipFree(ix->d_i8);
     if (ix->d_csum) (void)hipFree(ix->d_csum);
     if (ix->d_totals) (void)hipFree(ix->d_totals);
+    if (ix->groups) (void)hipFree(ix->groups);
+    if (ix->group_valid) (void)hipFree(ix->group_valid);
+    if (ix->d_group_fb) (void)hipFree(ix->d_group_fb);
     if (ix->h_totals) (void)hipHostFree(ix->h_totals);
     for (auto& kv : ix->uses) (void)hipEventDestroy(kv.second);
     if (ix->stream) (void)hipStreamDestroy(ix->stream);
@@ -927,6 +945,15 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "subset_wgs must be in [0, %d] (0 = auto)", kSubsetMaxSeg);
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->subset_wgs = value;
+    } else if (n == "group_fetch") {
+        if (value < 0 || value > kGroupMaxFetch)
+            return set_error(VDB_ERR_INVALID, "group_fetch must be in [0, %d] (0 = auto)", kGroupMaxFetch);
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->group_fetch = value;
+    } else if (n == "group_force_exact") {
+        if (value < 0 || value > 1) return set_error(VDB_ERR_INVALID, "group_force_exact must be 0 or 1");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->group_force_exact = value;
     } else if (n == "device_repass") {
         if (value < -1 || value > 1) return set_error(VDB_ERR_INVALID, "device_repass must be -1, 0 or 1");
         ix->device_repass = value;
@@ -1025,6 +1052,20 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "subset_rows") *value = ix->n_subset_rows.load();
     else if (n == "range_searches") *value = ix->n_range_searches.load();
     else if (n == "range_queries") *value = ix->n_range_queries.load();
+    else if (n == "group_rows") *value = ix->group_set ? ix->group_n : 0;
+    else if (n == "group_sets") *value = ix->n_group_sets.load();
+    else if (n == "group_searches") *value = ix->n_group_searches.load();
+    else if (n == "group_queries") *value = ix->n_group_queries.load();
+    else if (n == "group_fallback_queries") {  // counted by the select kernel: after the searches queued so far
+        unsigned long long fb = 0;
+        if (ix->d_group_fb) {
+            HIP_TRY(hipSetDevice(ix->device));
+            const int wr = wait_idle(ix);
+            if (wr) return wr;
+            HIP_TRY(hipMemcpy(&fb, ix->d_group_fb, sizeof(fb), hipMemcpyDeviceToHost));
+        }
+        *value = (int64_t)fb;
+    }
     else if (n == "subset_bad_ids") {  // counted by the kernel: after the row-list searches queued so far
         HIP_TRY(hipSetDevice(ix->device));
         const int wr = wait_idle(ix);
@@ -1206,6 +1247,7 @@ int32_t vdb_index_add(vdb_index* ix, const float* vectors, int64_t n, int32_t me
     ix->xres_abs = xm[2];
     ix->xres_dir = xm[3];
     ix->count += n;
+    ix->group_set = false;  // the group column covered the old rows only
     ix->auto_hold = 0;  // new rows: VDB_PREC_AUTO tries the one-plane passes again
     ix->auto_fails = 0;
     ix->auto_hold8 = 0;
@@ -1244,6 +1286,7 @@ static int32_t clear_locked(vdb_index* ix) {
     HIP_TRY(hipStreamSynchronize(ix->stream));
     std::memset(ix->i8st, 0, sizeof(ix->i8st));
     ix->count = 0;
+    ix->group_set = false;
     ix->auto_hold = 0;
     ix->auto_fails = 0;
     ix->auto_hold8 = 0;
@@ -1391,6 +1434,7 @@ int32_t vdb_index_remove(vdb_index* ix, const uint32_t* remove_mask, int32_t mem
 #undef RM_TRY
     (void)done(VDB_OK);
     ix->count = kept;
+    ix->group_set = false;  // the rows moved: the group column no longer lines up
     ix->gen++;
     ix->n_rows_removed += N - kept;
     ix->auto_hold = 0;  // the rows changed: VDB_PREC_AUTO tries the one-plane passes again
@@ -2595,6 +2639,225 @@ int32_t vdb_index_search_range(vdb_index* ix, const float* queries, int32_t B, c
     }
     ix->n_range_searches++;
     ix->n_range_queries += B;
+    return VDB_OK;
+}
+
+int32_t vdb_index_set_groups(vdb_index* ix, const int32_t* groups, int64_t n, int32_t mem, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::shared_mutex> g(ix->mu);
+    if (!group_set_ok(groups != nullptr, n, ix->count))
+        return set_error(VDB_ERR_INVALID, groups ? "the group column has %lld rows, the index %lld"
+                                                 : "a NULL group column detaches: n must be 0 (got %lld)",
+                         (long long)n, (long long)ix->count);
+    // queued device-memory searches on caller streams read the column this call replaces
+    {
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+    }
+    if (!groups) {  // detach
+        ix->group_set = false;
+        return VDB_OK;
+    }
+    hipStream_t st = ix->stream;
+    const int64_t n_words = (n + 31) / 32;
+    if (n > ix->group_cap || !ix->groups) {  // (+ 64 words: the candidate passes read whole mask tiles)
+        const int64_t cap = round_up(std::max<int64_t>(n, 1), kRowAlign);
+        int32_t* gnew = nullptr;
+        uint32_t* vnew = nullptr;
+        HIP_TRY(hipMalloc(&gnew, (size_t)cap * sizeof(int32_t)));
+        const hipError_t e = hipMalloc(&vnew, (size_t)(cap / 32 + 64) * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipFree(gnew);
+            HIP_TRY(e);
+        }
+        if (ix->groups) (void)hipFree(ix->groups);
+        if (ix->group_valid) (void)hipFree(ix->group_valid);
+        ix->groups = gnew;
+        ix->group_valid = vnew;
+        ix->group_cap = cap;
+        ix->group_set = false;
+    }
+    if (!ix->d_group_fb) {
+        HIP_TRY(hipMalloc(&ix->d_group_fb, 2 * sizeof(unsigned long long)));
+        HIP_TRY(zero_now(ix->d_group_fb, 2 * sizeof(unsigned long long), st));
+    }
+    ix->group_set = false;  // until the new column and its bitmap are whole
+    unsigned long long* n_valid = ix->d_group_fb + 1;
+    if (n > 0) {
+        if (mem == VDB_MEM_DEVICE) {
+            // the ids may still be being written on the caller's stream: the copy starts after that work
+            hipEvent_t ready = nullptr;
+            HIP_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+            hipError_t e = hipEventRecord(ready, (hipStream_t)stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(st, ready, 0);
+            (void)hipEventDestroy(ready);
+            HIP_TRY(e);
+        }
+        HIP_TRY(hipMemcpyAsync(ix->groups, groups, (size_t)n * sizeof(int32_t),
+                               mem == VDB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipMemsetAsync(ix->group_valid, 0, (size_t)(ix->group_cap / 32 + 64) * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(n_valid, 0, sizeof(unsigned long long), st));
+    HIP_TRY(launch_group_valid(ix->groups, n, ix->group_valid, n_words, n_valid, st));
+    unsigned long long nv = 0;
+    HIP_TRY(hipMemcpyAsync(&nv, n_valid, sizeof(nv), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ix->group_valid_rows = (int64_t)nv;
+    ix->group_any_neg = (int64_t)nv < n;
+    ix->group_n = n;
+    ix->group_set = true;
+    ix->n_group_sets++;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_groups(vdb_index* ix, const float* queries, int32_t B, int32_t k, const uint32_t* row_mask,
+                                int32_t mem, float* out_scores, int64_t* out_indices, int32_t* out_groups,
+                                double* out_keys, int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (B == 0) return VDB_OK;
+    const int D = ix->dim;
+    const bool host = mem == VDB_MEM_HOST;
+    // everything checked before any launch (the column itself under the lock, below)
+    switch (group_validate(B, k, queries != nullptr, out_scores != nullptr, out_indices != nullptr,
+                           out_groups != nullptr, mem, true, 0, 0)) {
+        case kGroupBadQueries:
+            return set_error(VDB_ERR_INVALID, "n_queries must be in [0, %d], got %d", kGroupMaxQueries, B);
+        case kGroupBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", kGroupMaxK, k);
+        case kGroupNullPointer:
+            return set_error(VDB_ERR_INVALID, "NULL query/output pointer (out_groups is required)");
+        case kGroupBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+        default: break;
+    }
+    if (host && !all_finite(queries, (int64_t)B * D)) return set_error(VDB_ERR_NONFINITE, "query contains NaN or Inf");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    if (group_validate(B, k, true, true, true, true, mem, ix->group_set, ix->group_n, N) == kGroupNoColumn)
+        return set_error(VDB_ERR_INVALID, "no group column is attached (vdb_index_set_groups; add, remove and clear drop it)");
+    // as vdb_index_search_rows: the caller's stream (device memory: NULL = the null stream), or for
+    // a host-memory call without one the stream of the workspace it takes
+    const bool own_stream = host && !stream;
+    hipStream_t st = own_stream ? nullptr : (hipStream_t)stream;
+    Workspace* w = acquire_ws(ix, st, own_stream);
+    if (own_stream) {
+        if (!w->own) {
+            const hipError_t e = hipStreamCreateWithFlags(&w->own, hipStreamNonBlocking);
+            if (e != hipSuccess) {
+                std::lock_guard<std::mutex> lg(ix->ws_mu);
+                w->busy = false;
+                return set_error(VDB_ERR_HIP, "workspace stream: %s", hipGetErrorString(e));
+            }
+        }
+        st = w->own;
+    }
+    struct Releaser {
+        vdb_index* ix; Workspace* w; hipStream_t st;
+        ~Releaser() { release_ws(ix, w, st); }
+    } rel{ix, w, st};
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const bool force = ix->group_force_exact != 0;
+    const int kf = group_fetch_k(ix->group_fetch, k);
+    const int n_seg = N > 0 ? group_n_seg(N, B, k) : 1;
+    const GroupScratch sc = group_scratch(B, D, k, kf, n_seg, N, host, masked, out_keys != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    const float* Qd = queries;
+    const uint32_t* cm = masked ? row_mask : nullptr;  // the caller's mask, on the device
+    float* out_s = out_scores;
+    int64_t* out_i = out_indices;
+    int32_t* out_g = out_groups;
+    double* out_k = out_keys;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = ws_host_io(w, (size_t)(sc.in_bytes + sc.out_bytes));
+        if (rc) return rc;
+        char* h = w->host_io;
+        std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+        if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+        HIP_TRY(hipMemcpyAsync(dev + sc.in0, h, (size_t)sc.in_bytes, hipMemcpyHostToDevice, st));
+        Qd = reinterpret_cast<const float*>(dev + sc.q);
+        cm = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        out_g = reinterpret_cast<int32_t*>(dev + sc.out_g);
+        out_k = out_keys ? reinterpret_cast<double*>(dev + sc.out_k) : nullptr;
+    }
+    if (N == 0) {  // an empty index: every slot "no result", as a search
+        HIP_TRY(launch_empty_results((int64_t)B * k, out_s, out_i, out_k, st));
+        HIP_TRY(hipMemsetAsync(out_g, 0xFF, (size_t)B * k * sizeof(int32_t), st));
+    } else {
+        // the mask of this call: the rows with a group AND the caller's rows
+        const uint32_t* fm = nullptr;
+        unsigned long long* elig_dev = nullptr;  // a masked call's eligible rows, counted on the device
+        if (cm) {
+            uint32_t* both = reinterpret_cast<uint32_t*>(dev + sc.fmask);
+            elig_dev = reinterpret_cast<unsigned long long*>(dev + sc.elig);
+            HIP_TRY(hipMemsetAsync(elig_dev, 0, sizeof(unsigned long long), st));
+            HIP_TRY(launch_group_and(cm, ix->group_valid, both, sc.mask_words, elig_dev, st));
+            fm = both;
+        } else if (ix->group_any_neg) {
+            fm = ix->group_valid;
+        }
+        double* qn64 = reinterpret_cast<double*>(dev + sc.qn64);
+        int* done = reinterpret_cast<int*>(dev + sc.done);
+        int* need = reinterpret_cast<int*>(dev + sc.need);
+        float* fs = reinterpret_cast<float*>(dev + sc.fs);
+        int64_t* fi = reinterpret_cast<int64_t*>(dev + sc.fi);
+        double* fk = reinterpret_cast<double*>(dev + sc.fk);
+        if (!force) {
+            // step 1: the best kf eligible rows with their keys, by the ordinary search in device
+            // memory on this stream (its own workspace, certificate and gated fallback; it counts
+            // the call in "searches" / "queries")
+            SearchOpts o;
+            rc = search_locked(ix, Qd, B, kf, fm, VDB_MEM_DEVICE, fs, fi, fk, 0, st, nullptr, o);
+            if (rc == kRetryBf16x3) {
+                o.force_b3 = true;
+                rc = search_locked(ix, Qd, B, kf, fm, VDB_MEM_DEVICE, fs, fi, fk, 0, st, nullptr, o);
+            }
+            if (rc) return rc;
+        } else {
+            ix->n_searches++;
+            ix->n_queries += B;
+        }
+        // the canonical query norms and the zeroed per-query counters of the fallback
+        HIP_TRY(launch_prep_queries(Qd, B, B, D, ix->G, ix->metric, nullptr, nullptr, qn64, nullptr, nullptr, nullptr,
+                                    nullptr, done, st));
+        GroupSelectArgs sa{};
+        sa.fs = fs; sa.fi = fi; sa.fk = fk; sa.k_fetch = kf;
+        sa.groups = ix->groups; sa.count = N; sa.k = k; sa.force = force ? 1 : 0;
+        sa.eligible = ix->group_valid_rows; sa.eligible_dev = elig_dev;
+        sa.need = need; sa.fallback_total = ix->d_group_fb;
+        sa.out_s = out_s; sa.out_i = out_i; sa.out_g = out_g; sa.out_k = out_k; sa.index_offset = index_offset;
+        HIP_TRY(launch_group_select(sa, B, st));
+        // step 3, gated per query on the device: nothing to wait for
+        GroupExactArgs ea{};
+        ea.Q = Qd; ea.qn64 = qn64; ea.X = ix->X; ea.G = ix->G; ea.D = D; ea.nrm64 = ix->nrm64; ea.N = N;
+        ea.mask = fm; ea.groups = ix->groups; ea.need = need; ea.k = k;
+        ea.lk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.lk) : nullptr;
+        ea.lr = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.lr) : nullptr;
+        ea.lg = n_seg > 1 ? reinterpret_cast<int32_t*>(dev + sc.lg) : nullptr;
+        ea.done = done;
+        ea.out_s = out_s; ea.out_i = out_i; ea.out_g = out_g; ea.out_k = out_k; ea.index_offset = index_offset;
+        HIP_TRY(launch_group_exact(ix->metric, ea, B, n_seg, st));
+    }
+    if (host) {
+        char* r = w->host_io + sc.in_bytes;
+        HIP_TRY(hipMemcpyAsync(r, dev + sc.out0, (size_t)sc.out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+        std::memcpy(out_groups, r + (sc.out_g - sc.out0), (size_t)B * k * 4);
+        if (out_keys) std::memcpy(out_keys, r + (sc.out_k - sc.out0), (size_t)B * k * 8);
+    }
+    if (N == 0) {  // (a non-empty index's call was counted by its inner search)
+        ix->n_searches++;
+        ix->n_queries += B;
+    }
+    ix->n_group_searches++;
+    ix->n_group_queries += B;
     return VDB_OK;
 }
 

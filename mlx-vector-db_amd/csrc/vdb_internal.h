@@ -369,6 +369,40 @@ struct RangeArgs {
 };
 hipError_t launch_range_block(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st);
 
+// Grouped search (vdb_group.hip, vdb_index_search_groups).  The column's bitmap: bit r of word r / 32
+// = row r < n has a group id >= 0 (n_words words written whole), *n_valid += those rows; and out =
+// a & b over n_words words (the caller's row mask with that bitmap), *n_set += the bits set in it.
+hipError_t launch_group_valid(const int32_t* groups, int64_t n, uint32_t* bitmap, int64_t n_words,
+                              unsigned long long* n_valid, hipStream_t st);
+hipError_t launch_group_and(const uint32_t* a, const uint32_t* b, uint32_t* out, int64_t n_words,
+                            unsigned long long* n_set, hipStream_t st);
+// The select: query b's fetched list fs / fi / fk [b][k_fetch] (local rows, -1 = none, ranked by (key
+// desc, row asc), every row with a group) -> its first k distinct groups' rows in out_* [b][k], or,
+// when the list does not settle the query (vdb_group_plan.h group_complete; force: always), need[b]
+// = 1 and *fallback_total += 1 with nothing written.  eligible: the rows the fetch could return in
+// all (*eligible_dev if set, a masked call's count).  One workgroup per query; k_fetch <= 256.
+struct GroupSelectArgs {
+    const float* fs; const int64_t* fi; const double* fk; int k_fetch;
+    const int32_t* groups; int64_t count; int k; int force;
+    int64_t eligible; const unsigned long long* eligible_dev;
+    int* need; unsigned long long* fallback_total;
+    float* out_s; int64_t* out_i; int32_t* out_g; double* out_k; int64_t index_offset;
+};
+hipError_t launch_group_select(const GroupSelectArgs& a, int n_queries, hipStream_t st);
+// The exact fallback: grid (n_seg, n_queries); the workgroups of a query with need[b] == 0 return at
+// once.  Segment s scans rows group_seg_range(N, n_seg, s) whose mask bit (optional) is set and whose
+// group id is >= 0; with n_seg > 1 the workgroup that finishes a query last merges the segments'
+// lists lk / lr / lg [n_queries][n_seg][k] (done [n_queries]: zero on entry, zero again on exit) and
+// writes out_* [b][k].  N >= 1.
+struct GroupExactArgs {
+    const float* Q; const double* qn64; const float* X; int G; int D; const double* nrm64; int64_t N;
+    const uint32_t* mask; const int32_t* groups; const int* need; int k;
+    double* lk; uint32_t* lr; int32_t* lg; int* done;
+    float* out_s; int64_t* out_i; int32_t* out_g; double* out_k; int64_t index_offset;
+};
+size_t group_exact_lds_bytes(int k);
+hipError_t launch_group_exact(int metric, const GroupExactArgs& a, int n_queries, int n_seg, hipStream_t st);
+
 // Merge sorted fp64-key lists.  Element (q, j, e) lives at q*sq + j*sj + e, lists
 // have Lk entries; output [nq][KP] sorted.
 hipError_t launch_merge_f64_u32(int KP, const double* lk, const uint32_t* li, int n_lists, int Lk,

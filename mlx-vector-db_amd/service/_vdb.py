@@ -41,7 +41,8 @@ EXPORTED_SYMBOLS = (
     "vdb_index_set_param", "vdb_index_get_stat",
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
-    "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
+    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -105,6 +106,9 @@ def load_library():
                                               c_vp, c_i64, c_vp]),
             "vdb_index_search_range": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64,
                                                c_vp]),
+            "vdb_index_set_groups": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
+            "vdb_index_search_groups": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                                c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -463,6 +467,69 @@ class NativeIndex:
             self._h, ctypes.c_void_p(q_ptr), int(n_queries), ctypes.c_void_p(thresholds_ptr),
             ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, int(cap), ctypes.c_void_p(out_counts_ptr),
             ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_scores_ptr or None),
+            ctypes.c_void_p(out_keys_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
+
+    # -- grouped search ----------------------------------------------------------
+    def set_groups(self, groups) -> None:
+        """include/vdb.h vdb_index_set_groups, host memory: attach one int32 group id per row
+        (``len(groups) == count``; a negative id = the row has no group).  ``None`` detaches the
+        column.  Every add, remove and clear drops it; an update keeps it."""
+        if groups is None:
+            _check(self._lib.vdb_index_set_groups(self._h, None, 0, MEM_HOST, None))
+            return
+        g = np.asarray(groups)
+        if g.size and g.dtype.kind not in "iu":
+            raise ValueError(f"group ids must be integers, got dtype {g.dtype}")
+        if g.size and (int(g.min()) < -2**31 or int(g.max()) >= 2**31):
+            raise ValueError("group ids must fit int32")
+        g = np.ascontiguousarray(g.reshape(-1), dtype=np.int32)
+        # (an empty array still attaches -- to an empty index: a pointer the library never reads)
+        _check(self._lib.vdb_index_set_groups(self._h, _ptr(g) if g.size else _ptr(np.zeros(1, np.int32)), g.size,
+                                              MEM_HOST, None))
+
+    def set_groups_device(self, ptr: int, n: int, stream: int = 0) -> None:
+        """vdb_index_set_groups with a device-memory int32 column, read after the work queued on
+        ``stream``."""
+        _check(self._lib.vdb_index_set_groups(self._h, ctypes.c_void_p(ptr or None), int(n), MEM_DEVICE,
+                                              ctypes.c_void_p(stream or None)))
+
+    def search_groups(self, queries: np.ndarray, k: int, row_mask: Optional[np.ndarray] = None,
+                      with_keys: bool = False, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_groups, host memory: the k best distinct groups of each
+        query, slot j holding the best row of the j-th group.  Returns (scores f32 [B,k], indices
+        i64 [B,k], groups i32 [B,k][, keys f64 [B,k]]); slots past the number of eligible groups
+        are 0 / -1 / -1 / -inf."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must have shape (B, {self.dim}), got {np.shape(queries)}")
+        B = q.shape[0]
+        k = int(k)
+        scores = np.empty((B, max(k, 0)), dtype=np.float32)  # (a bad k is the library's to refuse)
+        idx = np.empty((B, max(k, 0)), dtype=np.int64)
+        grp = np.empty((B, max(k, 0)), dtype=np.int32)
+        keys = np.empty((B, max(k, 0)), dtype=np.float64) if with_keys else None
+        mask_p = None
+        if row_mask is not None:
+            m = np.ascontiguousarray(row_mask, dtype=np.uint32)
+            need = (self.count() + 31) // 32
+            if m.size < need:
+                raise ValueError(f"row_mask needs {need} uint32 words, got {m.size}")
+            mask_p = _ptr(m)
+        _check(self._lib.vdb_index_search_groups(self._h, _ptr(q), B, k, mask_p, MEM_HOST, _ptr(scores), _ptr(idx),
+                                                 _ptr(grp), _ptr(keys) if keys is not None else None,
+                                                 int(index_offset), None))
+        return (scores, idx, grp, keys) if with_keys else (scores, idx, grp)
+
+    def search_groups_device(self, q_ptr: int, n_queries: int, k: int, out_scores_ptr: int, out_idx_ptr: int,
+                             out_groups_ptr: int, out_keys_ptr: int = 0, mask_ptr: int = 0, index_offset: int = 0,
+                             stream: int = 0) -> None:
+        """vdb_index_search_groups with device-memory arguments; stream-ordered, nothing is read
+        back."""
+        _check(self._lib.vdb_index_search_groups(
+            self._h, ctypes.c_void_p(q_ptr), int(n_queries), int(k), ctypes.c_void_p(mask_ptr or None), MEM_DEVICE,
+            ctypes.c_void_p(out_scores_ptr), ctypes.c_void_p(out_idx_ptr), ctypes.c_void_p(out_groups_ptr or None),
             ctypes.c_void_p(out_keys_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
 
 

@@ -127,6 +127,30 @@ class MetadataIndex:
                 return np.zeros(0, np.int64)
             return np.sort(np.frombuffer(lst, dtype=np.int64))
 
+    def group_column(self, key: Any, n: int) -> Tuple[np.ndarray, List[Any]]:
+        """(int32 [n] group id per row, values): row r's id is the position in ``values`` of its
+        metadata's value for ``key``; the ids are 0..G-1 in the order of each value's first row.  A
+        row without the key, or holding it with a value the postings skip (unhashable, NaN), gets
+        -1: the column the device's grouped search takes (include/vdb.h vdb_index_set_groups).
+        Built from the postings of ``key`` alone, O(rows holding it), not by a scan of the dicts."""
+        col = np.full(max(int(n), 0), -1, dtype=np.int32)
+        with self._lock:
+            by_val = self._post.get(key) if _hashable(key) else None
+            if not by_val:
+                return col, []
+            firsts = []
+            for val, lst in by_val.items():
+                a = np.frombuffer(lst, dtype=np.int64)
+                a = a[a < n]
+                if a.size:
+                    firsts.append((int(a.min()), val, a))
+            firsts.sort(key=lambda t: t[0])  # (a row holds one value per key: the first rows differ)
+            values = []
+            for gid, (_, val, a) in enumerate(firsts):
+                col[a] = gid
+                values.append(val)
+            return col, values
+
     def replace(self, rows, metadata: List[Dict]) -> None:
         """Row rows[i] now has metadata[i] (ids in [0, len), pairwise distinct): the postings lose
         the old dicts' pairs and gain the new ones', O(pairs of those rows) dictionary work plus

@@ -44,6 +44,10 @@ logger = logging.getLogger("mlx_vector_db.optimized_store")
 # Raised by the reference when no similarity operator exists (jit_compile=False
 # or metric="dot_product"): service/optimized_vector_store.py:153-154.
 _NO_OPERATOR_MSG = "Keine kompilierte Ähnlichkeitsfunktion verfügbar."
+# query_groups: the most groups per query (include/vdb.h vdb_index_search_groups) and the most hits
+# per group; POST /vectors/query_groups bounds its body by the same two
+GROUP_MAX_K = 128
+GROUP_MAX_SIZE = 100
 
 
 # half the smallest measured crossover of the row-list search against the masked
@@ -267,6 +271,12 @@ class MLXVectorStore:
         self._metadata: List[Dict] = []
         self._meta_index = MetadataIndex()
         self._vector_count = 0
+        # query_groups: the one group column attached to the index, (key, rows, update count), its
+        # values and the index's "group_sets" when it was attached
+        self._group_lock = threading.Lock()
+        self._group_tag: Optional[Tuple] = None
+        self._group_values: List[Any] = []
+        self._group_sets = -1
         self._hnsw_index = None
         self._files = StoreFiles(self.store_path)
         self._coalescer = _QueryCoalescer(lambda Q, k, filters=None: self._search_filtered(
@@ -784,6 +794,117 @@ class MLXVectorStore:
                 ib = idx[b, :n][order].tolist()
                 sb = scores[b, :n][order].astype(np.float64).tolist()
                 out.append((ib, sb, [meta[i] if i < len(meta) else {} for i in ib], n))
+            return out
+
+    # ---- grouped query ---------------------------------------------------------------
+    def query_groups(self, query_vector: Union[np.ndarray, Any], group_by: str, k: int = 10, group_size: int = 1,
+                     filter_metadata: Optional[Dict] = None) -> List[Dict]:
+        """The ``k`` best distinct values of the metadata key ``group_by`` ("the k best documents,
+        with the best chunk of each") -> a list of ``{"group": value, "hits": (indices, scores,
+        metadata)}``, best group first; the hits are in the form ``query`` returns them, best
+        first, at most ``group_size`` per group.  A group ranks by its best row (the exact key
+        ``query`` ranks by, ties to the lower row); rows without the key belong to no group.
+        Exact (include/vdb.h vdb_index_search_groups): no over-fetch that one long document can
+        fill.  The reference has no such read: its RAG pipeline stores document_id beside every
+        chunk (integrations/mlx_lm_pipeline.py:656-670) and asks for the best k chunks."""
+        q = _as_matrix(query_vector)
+        if q.ndim == 2 and q.shape[0] == 1:
+            q = q[0]
+        if q.ndim != 1:
+            raise ValueError(f"query_groups takes one vector of shape (dim,) or (1, dim), got {q.shape}; "
+                             "use batch_query_groups for several")
+        return self._group_search(q[None, :], group_by, k, group_size, filter_metadata)[0]
+
+    def batch_query_groups(self, query_vectors: Union[np.ndarray, Any], group_by: str, k: int = 10,
+                           group_size: int = 1, filter_metadata: Optional[Dict] = None) -> List[List[Dict]]:
+        """``query_groups`` for a [B, dim] block of queries: one list of groups per query, from one
+        device call (two with ``group_size`` > 1)."""
+        q = _as_matrix(query_vectors)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError(f"query_vectors must be 2-D (B, dim), got {q.shape}")
+        return self._group_search(q, group_by, k, group_size, filter_metadata)
+
+    def _attach_groups(self, group_by) -> List[Any]:
+        """Make ``group_by``'s column the one attached to the index (read lock and _group_lock
+        held) -> its values, group id = position.  Kept while the key, the row count and the
+        rows' contents stay as they were and the index still holds it (an add, a delete and a
+        clear drop it; an upsert may change a row's value)."""
+        n = self._vector_count
+        tag = (group_by, n, self._index.stat("rows_updated"))
+        if self._group_tag == tag and self._index.stat("group_rows") == n \
+                and self._index.stat("group_sets") == self._group_sets:
+            return self._group_values
+        col, values = self._meta_index.group_column(group_by, n)
+        self._group_tag = None
+        if not values:  # no row has the key: nothing is searched, and no other key's column stays attached
+            if self._index.stat("group_rows"):
+                self._index.set_groups(None)
+        else:
+            self._index.set_groups(col)
+            self._group_tag, self._group_values = tag, values
+            self._group_sets = self._index.stat("group_sets")
+        return values
+
+    def _group_search(self, Q: np.ndarray, group_by, k: int, group_size: int, filter_metadata: Optional[Dict]):
+        if len(self._devices()) > 1:
+            raise NotImplementedError("grouped query is not supported on a multi-device store")
+        k, group_size = int(k), int(group_size)
+        if not 1 <= k <= GROUP_MAX_K:
+            raise ValueError(f"k must be in [1, {GROUP_MAX_K}], got {k}")
+        if not 1 <= group_size <= GROUP_MAX_SIZE:
+            raise ValueError(f"group_size must be in [1, {GROUP_MAX_SIZE}], got {group_size}")
+        B = Q.shape[0]
+        with _Read(self._rw):
+            # (never the graph path, never the coalescer: one exact device call for the block)
+            mask = self._range_mask(Q, filter_metadata)  # None: no filter; False: nothing to search
+            if mask is False or B == 0:
+                return [[] for _ in range(B)]
+            n = self._vector_count
+            with self._group_lock:  # one attached column: attach and search as one step
+                values = self._attach_groups(group_by)
+                if not values:  # no row has the key
+                    return [[] for _ in range(B)]
+                scores, idx, grp = self._index.search_groups(Q, k, row_mask=mask)
+            meta = self._metadata
+
+            def hits_of(rows, sc):
+                return (rows, sc, [meta[i] if i < len(meta) else {} for i in rows])
+
+            out = []
+            if group_size == 1:
+                for b in range(B):
+                    valid = idx[b] >= 0
+                    out.append([{"group": values[g], "hits": hits_of([int(i)], [float(s)])}
+                                for i, s, g in zip(idx[b][valid], scores[b][valid].astype(np.float64), grp[b][valid])])
+                return out
+            # group_size > 1: every returned group's own rows, searched as row lists (one list per
+            # distinct group of the batch, shared between the queries that returned it)
+            filt_rows = self._meta_index.rows(filter_metadata, n) if filter_metadata else None
+            list_of: Dict[int, int] = {}
+            lists, members, qlist = [], [], []
+            for b in range(B):
+                for g in grp[b][idx[b] >= 0].tolist():
+                    if g not in list_of:
+                        rows = self._meta_index.rows_with(group_by, values[g])
+                        rows = rows[rows < n]
+                        if filt_rows is not None:
+                            rows = np.intersect1d(rows, filt_rows, assume_unique=True)
+                        list_of[g] = len(lists)
+                        lists.append(rows)
+                    members.append(b)
+                    qlist.append(list_of[g])
+            if not members:
+                return [[] for _ in range(B)]
+            kk = min(group_size, max(r.size for r in lists))
+            s2, i2 = self._index.search_rows(Q[members], kk, lists, query_list=np.asarray(qlist, np.int32))
+            out = [[] for _ in range(B)]
+            gids = [g for b in range(B) for g in grp[b][idx[b] >= 0].tolist()]
+            for j, (b, g) in enumerate(zip(members, gids)):
+                valid = i2[j] >= 0
+                out[b].append({"group": values[g],
+                               "hits": hits_of(i2[j][valid].tolist(), s2[j][valid].astype(np.float64).tolist())})
             return out
 
     # ---- misc API ----------------------------------------------------------------------
