@@ -1,5 +1,6 @@
 // vdb_api.cpp — the C-ABI (include/vdb.h): index object, workspace pool and the
-// search driver that sequences the kernels of vdb_kernels.hip.
+// search driver that sequences the kernels of the vdb_*.hip files (launchers: vdb_internal.h);
+// the host arithmetic of each entry point lives in its vdb_*_plan.h.
 //
 // Host-side restatement of the reference store's operator flow
 // (service/optimized_vector_store.py:96-192): ingest appends rows in place and
@@ -26,6 +27,7 @@
 #include "vdb_subset_plan.h"
 #include "vdb_range_plan.h"
 #include "vdb_group_plan.h"
+#include "vdb_search_plan.h"
 #include "vdb_internal.h"
 
 using namespace vdb;
@@ -55,7 +57,6 @@ int set_error(int code, const char* fmt, ...) {
 constexpr int64_t kRowAlign = ROW_ALIGN;   // capacity granule, a multiple of every scan step
 
 constexpr size_t kGatedExactBytes = 256u << 20;  // device-gated fallback lists sized for every query of a batch
-constexpr int kMaxApproxK = 200;          // k above this uses the exact path
 constexpr int kSubsetBadWord = 12;        // d_xmax word (8 bytes each) counting a row-list search's skipped ids
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
@@ -82,7 +83,7 @@ struct Workspace {
     char* dev = nullptr;
     size_t dev_bytes = 0;
     char* exact = nullptr;  // exact-path lists, grown on demand
-    size_t exact_bytes = 0;
+    size_t exact_cap = 0;
     int* host_flag = nullptr;  // pinned
     // pinned staging of a host-memory search: the queries up, the results down (read with the
     // certificate's flags in one synchronisation; grown on demand)
@@ -274,7 +275,7 @@ void free_workspace_memory(Workspace* w) {
     w->exact = nullptr;
     w->host_flag = nullptr;
     w->host_io = nullptr;
-    w->dev_bytes = w->exact_bytes = w->host_io_bytes = 0;
+    w->dev_bytes = w->exact_cap = w->host_io_bytes = 0;
 }
 
 int wait_idle(vdb_index* ix);
@@ -638,14 +639,14 @@ int ws_host_io(Workspace* w, size_t bytes) {
 }
 
 int ws_reserve_exact(Workspace* w, size_t bytes, hipStream_t st) {
-    if (bytes > w->exact_bytes) {
+    if (bytes > w->exact_cap) {
         if (w->exact) {
             HIP_TRY(hipStreamSynchronize(st));
             (void)hipFree(w->exact);
             w->exact = nullptr;
         }
         HIP_TRY(hipMalloc(&w->exact, bytes));
-        w->exact_bytes = bytes;
+        w->exact_cap = bytes;
     }
     return VDB_OK;
 }
@@ -656,49 +657,145 @@ bool all_finite(const float* p, int64_t n) {
     return true;
 }
 
+// ---- the call frame the entry points share -------------------------------------------------------
+// A search's stream and workspace, for the length of the call.  Device memory: the caller's
+// stream, NULL = the null stream (ordered with the caller's default-stream work, e.g. PyTorch's);
+// host memory: the caller's stream, or (NULL) the stream of the workspace the call takes, created
+// on first use, so concurrent host searches overlap.  rc != 0: no workspace is held and the error
+// is set.  The workspace goes back (its event recorded on the stream) when the lease ends.
+struct SearchLease {
+    vdb_index* ix;
+    Workspace* w = nullptr;
+    hipStream_t st = nullptr;
+    int rc = VDB_OK;
+    SearchLease(vdb_index* ix_, int32_t mem, void* stream) : ix(ix_) {
+        const bool own_stream = mem == VDB_MEM_HOST && !stream;
+        st = own_stream ? nullptr : (hipStream_t)stream;
+        w = acquire_ws(ix, st, own_stream);
+        if (!own_stream) return;
+        if (!w->own) {
+            const hipError_t e = hipStreamCreateWithFlags(&w->own, hipStreamNonBlocking);
+            if (e != hipSuccess) {
+                {
+                    std::lock_guard<std::mutex> lg(ix->ws_mu);
+                    w->busy = false;
+                }
+                w = nullptr;
+                rc = set_error(VDB_ERR_HIP, "workspace stream: %s", hipGetErrorString(e));
+                return;
+            }
+        }
+        st = w->own;
+    }
+    ~SearchLease() {
+        if (w) release_ws(ix, w, st);
+    }
+    SearchLease(const SearchLease&) = delete;
+    SearchLease& operator=(const SearchLease&) = delete;
+};
 
-// query slots of the device-gated exact scan (each loops over the flagged queries)
-constexpr int kGateSlots = 4;
-
-// Exact full scan for queries qlist[0..nq) (device list) -> writes outputs.
-// Bytes of the exact path's lists for nq queries (device-gated form: one list per CU).
-size_t exact_bytes(vdb_index* ix, int nq, int k, bool gated) {
-    const int KE = std::max(32, next_pow2(k));
-    const int64_t n_wg = std::min<int64_t>(std::max<int64_t>(1, ix->n_cu * (gated ? 1 : 2)),
-                                           std::max<int64_t>(1, ix->count / 256));
-    return (size_t)nq * n_wg * KE * (sizeof(double) + sizeof(uint32_t)) + (size_t)nq * KE * 12 + 4096 +
-           (gated ? exact_scan_scratch_bytes(KE, (int)n_wg, std::min(nq, kGateSlots)) : 0);
+// `st` runs what follows after the work queued so far on the caller's stream (NULL = the null
+// stream): device-memory arguments may still be being written there.
+hipError_t order_after_caller(hipStream_t st, void* caller_stream) {
+    hipEvent_t ready = nullptr;
+    hipError_t e = hipEventCreateWithFlags(&ready, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+    e = hipEventRecord(ready, (hipStream_t)caller_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, ready, 0);
+    (void)hipEventDestroy(ready);
+    return e;
 }
 
-// Exact scan of the queries qlist[0..nq) (or 0..nq).  Device-gated form (qcount_dev):
-// the flagged count is read on the device, nq is the capacity, and nothing runs
-// when no query was flagged.
+// Host-memory staging of the plan-style entry points (row-list, range and grouped search; their
+// *_scratch() keeps the arguments in [in0, in0 + in_bytes) of the workspace and the results in
+// [out0, out0 + out_bytes)).  Up: pack(h) writes the arguments into the pinned buffer h, which goes
+// up in one copy.
+template <typename Pack>
+int stage_up(Workspace* w, int64_t in0, int64_t in_bytes, int64_t out_bytes, hipStream_t st, Pack&& pack) {
+    const int rc = ws_host_io(w, (size_t)(in_bytes + out_bytes));
+    if (rc) return rc;
+    pack(w->host_io);
+    HIP_TRY(hipMemcpyAsync(w->dev + in0, w->host_io, (size_t)in_bytes, hipMemcpyHostToDevice, st));
+    return VDB_OK;
+}
+// Down: the results in one copy, complete on return, at *r (the pinned buffer, out0's bytes first).
+int stage_down(Workspace* w, int64_t in_bytes, int64_t out0, int64_t out_bytes, hipStream_t st, const char** r) {
+    *r = w->host_io + in_bytes;
+    HIP_TRY(hipMemcpyAsync(w->host_io + in_bytes, w->dev + out0, (size_t)out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return VDB_OK;
+}
+
+
+// The index's knobs for the main search's plan (i8_narrow: the policy's answer, see search_locked).
+SearchKnobs search_knobs(const vdb_index* ix, bool i8_narrow) {
+    SearchKnobs kn{};
+    kn.force_exact = ix->force_exact != 0;
+    kn.margin = ix->margin;
+    kn.i8_narrow = i8_narrow;
+    kn.scan_q4 = ix->scan_q4;
+    kn.scan_wide = ix->scan_wide;
+    kn.n_wg_override = ix->n_wg_override;
+    kn.scan_variant = ix->scan_variant;
+    kn.scan_sync = ix->scan_sync;
+    kn.finish_split = ix->finish_split;
+    kn.i8_refine = ix->i8_refine;
+    kn.scan_checksum = ix->scan_checksum;
+    kn.pilot_tiles = ix->pilot_tiles;
+    kn.pilot_rank_override = ix->pilot_rank_override;
+    kn.has_xh = ix->Xh != nullptr;
+    kn.has_csum = ix->d_csum != nullptr;
+    return kn;
+}
+
+// What the candidate passes' own files say about this call (the plan never calls into them).
+SearchKernelFacts kernel_facts(const SearchShape& s, const SearchKnobs& kn, const SearchKP& kp) {
+    SearchKernelFacts f{};
+    const int Gs = search_groups(s.prec, s.G);
+    if (prec_is_i8(s.prec)) {
+        f.scan8wl_ok = scan8wl_ok(s.prec, s.metric, Gs, s.B);
+        f.scan8w_ok = scan8w_ok(Gs, s.B);
+        f.rows_per_step = scan8_rows_per_step(s.prec, s.metric);
+    } else if (s.prec == PREC_BF16X3 || s.prec == PREC_BF16) {
+        f.rows_per_step = scan2_rows_per_step(false);
+        f.rows_per_step_q4 = scan2_rows_per_step(true);
+    } else {
+        f.scan_variant_ok = scan_variant_ok(s.prec, (int)kn.scan_variant, Gs);
+        const int v = f.scan_variant_ok ? (int)kn.scan_variant : 0;
+        f.rows_per_step = scan_rows_per_step(s.prec, v);
+        f.scan_priv = scan_priv(s.prec, v, kp.KP);
+    }
+    return f;
+}
+
+// Bytes a device-memory batch's gated fallback is judged by (exact_gate_bytes, vdb_search_plan.h).
+size_t gated_exact_bytes(const vdb_index* ix, int nq, int k) {
+    const ExactPlan ep = exact_plan(ix->count, ix->n_cu, nq, k, true);
+    return (size_t)exact_gate_bytes(ep, nq, (int64_t)exact_scan_scratch_bytes(ep.KE, ep.n_wg_gate, ep.slots));
+}
+
+// Exact scan of the queries qlist[0..nq) (or 0..nq) -> writes outputs.  Device-gated form
+// (qcount_dev): the flagged count is read on the device, nq is the capacity, and nothing runs
+// when no query was flagged.  The plan and the lists' layout: vdb_search_plan.h.
 int run_exact(vdb_index* ix, Workspace* w, const float* Qd, const double* qn64, const int* qlist_dev, int nq, int k,
               const uint32_t* mask_dev, float* out_s, int64_t* out_i, double* out_k, int64_t index_offset,
               const int64_t* row_ids, hipStream_t st, const int* qcount_dev = nullptr, const int* ovf_dev = nullptr,
               int* done_dev = nullptr, unsigned long long* host_totals = nullptr) {
-    const int KE = std::max(32, next_pow2(k));
     const int64_t N = ix->count;
     const bool gated = qcount_dev != nullptr;
-    // ~2 workgroups per CU of rows (gated: 1, since an empty gated launch still has to find free
-    // CUs beside the next batch's scan), at least 64 rows per wave
-    const int64_t wg_target = gated ? std::max<int64_t>(1, ix->n_cu) : 2 * ix->n_cu;
-    int n_wg = (int)std::min<int64_t>(wg_target, std::max<int64_t>(1, N / 256));
-    const int64_t rpw = (N + n_wg - 1) / n_wg;
-    n_wg = (int)((N + rpw - 1) / rpw);
-    const int n_lists = n_wg;
-    const size_t list_elems = (size_t)nq * n_lists * KE;
+    const ExactPlan ep = exact_plan(N, ix->n_cu, nq, k, gated);
+    const int KE = ep.KE, n_wg = ep.n_wg, n_lists = ep.n_wg;
+    const int64_t rpw = ep.rpw;
     // the device-gated form keeps its top-k buffers in the workspace (no LDS, vdb_exact.hip)
-    const size_t scr = gated && done_dev ? exact_scan_scratch_bytes(KE, n_wg, std::min(nq, kGateSlots)) : 0;
-    const size_t bytes = list_elems * (sizeof(double) + sizeof(uint32_t)) + (size_t)nq * KE * 12 + 4096 + scr;
-    int rc = ws_reserve_exact(w, bytes, st);
+    const ExactLayout el =
+        exact_layout(ep, nq, gated && done_dev ? (int64_t)exact_scan_scratch_bytes(KE, n_wg, ep.slots) : 0);
+    int rc = ws_reserve_exact(w, (size_t)el.total, st);
     if (rc) return rc;
-    Carver c{w->exact};
-    double* lk = c.take<double>(list_elems);
-    uint32_t* li = c.take<uint32_t>(list_elems);
-    double* mk = c.take<double>((size_t)nq * KE);
-    uint32_t* mi = c.take<uint32_t>((size_t)nq * KE);
-    char* gscr = scr ? c.take<char>(scr) : nullptr;
+    double* lk = reinterpret_cast<double*>(w->exact + el.lk);
+    uint32_t* li = reinterpret_cast<uint32_t*>(w->exact + el.li);
+    double* mk = reinterpret_cast<double*>(w->exact + el.mk);
+    uint32_t* mi = reinterpret_cast<uint32_t*>(w->exact + el.mi);
+    char* gscr = el.scr >= 0 ? w->exact + el.scr : nullptr;
     if (gated && done_dev) {  // one launch: the last workgroup per query merges and writes (ExactTail)
         const ExactTail tail{done_dev, mk, mi, k, index_offset, out_s, out_i, out_k, row_ids, host_totals};
         HIP_TRY(launch_exact_scan(ix->metric, KE, Qd, qn64, qlist_dev, nq, ix->X, ix->G, ix->dim, ix->nrm64, mask_dev,
@@ -1161,12 +1258,7 @@ int32_t vdb_index_add(vdb_index* ix, const float* vectors, int64_t n, int32_t me
     if (mem == VDB_MEM_DEVICE) {
         // the rows may still be being written on the caller's stream (NULL = the null stream):
         // ingest (on the index's own stream) starts after that work
-        hipEvent_t ready = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ready, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, ready, 0);
-        (void)hipEventDestroy(ready);
-        HIP_TRY(e);
+        HIP_TRY(order_after_caller(st, stream));
     }
     const int D = ix->dim;
     const int64_t chunk = std::max<int64_t>(1, (int64_t)(256ll << 20) / ((int64_t)D * 4));
@@ -1347,12 +1439,7 @@ int32_t vdb_index_remove(vdb_index* ix, const uint32_t* remove_mask, int32_t mem
         md = reinterpret_cast<const uint32_t*>(scan);
     } else {
         // the mask may still be being written on the caller's stream (NULL = the null stream)
-        hipEvent_t ready = nullptr;
-        RM_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ready, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, ready, 0);
-        (void)hipEventDestroy(ready);
-        RM_TRY(e);
+        RM_TRY(order_after_caller(st, stream));
     }
     Carver c{scan, mask_bytes};
     uint32_t* base = c.take<uint32_t>((size_t)n_words + 1);
@@ -1493,12 +1580,7 @@ int32_t vdb_index_update(vdb_index* ix, const int64_t* rows, const float* vector
     float* s_rows = host ? c.take<float>((size_t)chunk * D) : nullptr;
     if (!host) {
         // the ids and rows may still be being written on the caller's stream (NULL = the null stream)
-        hipEvent_t ready = nullptr;
-        UP_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ready, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, ready, 0);
-        (void)hipEventDestroy(ready);
-        UP_TRY(e);
+        UP_TRY(order_after_caller(st, stream));
     }
     // chunk [r, r + m) of the call on the device: staged (host memory; the staging is free again
     // once the stream has run what read it) or where the caller put it
@@ -1615,26 +1697,10 @@ constexpr int32_t kRetryBf16x3 = 1 << 20;
 // A host-memory bf16 search re-passes its uncertified queries in bf16x3 (gathered into one
 // device-memory sub-search) when they are at most 1/8 of the batch and at most this many.
 constexpr int kRepassMax = 64;
-// Device-memory searches (device_repass): up to this many uncertified queries of a batch are
-// gathered into a gated BF16X3 sub-search on the device (more go to the exact path); auto arms
-// the re-pass for kRepassArm searches after a device fallback was seen.
-constexpr int kRepassDev = 16;
+// Device-memory searches (device_repass): up to kRepassDev (vdb_search_plan.h) uncertified queries
+// of a batch take a gated sub-search on the device; auto arms the re-pass for this many searches
+// after a device fallback was seen.
 constexpr int kRepassArm = 256;
-// auto's I8 pass: KP = 128 up to this many rows (i8_narrow)
-constexpr int64_t kI8NarrowRows = 512 * 1024;
-constexpr int64_t kI8NarrowRowsShort = 4 * 1024 * 1024;  // rows of <= 128 dims
-// the wide int8 pass under scan_wide auto: from this many rows (smaller indexes: the 64-query shape)
-constexpr int64_t kWideMinRows = 65536;
-// ... and, for batches of <= 256 (a 64-query block's stage tiles split over 2..8 waves), up to this
-// many rows: the c6 shard of an 8-way run (1.25M x 128, B = 64) 1.03 -> 1.25 M QPS per rank, scan
-// 60 -> 40 us; at 10M rows the scan is faster (0.218 -> 0.206 ms) but the three-stream step slower
-// (0.235 -> 0.245: its 134 KiB of LDS leave no room for the other streams' side kernels),
-// profiles/r06_c6w2
-constexpr int64_t kWideSplitMaxRows = 2500000;
-// the finish holds every segment's entries: at most FIN_CAP (16 K) / W8_CH segments
-constexpr int FIN_SEG_MAX = 512;
-// i8_refine auto: the finish refines I8 candidates' scores for padded rows of this many dims or more
-constexpr int64_t kRefineMinDp = 512;
 // VDB_PREC_AUTO uses the bf16 pass up to this k (its KP = next_pow2(k + 112) stays 128)
 constexpr int kAutoBf16MaxK = 16;
 
@@ -1747,21 +1813,13 @@ static int32_t search_locked(vdb_index* ix, const float* queries, int32_t B, int
                              int32_t mem, float* out_scores, int64_t* out_indices, double* out_keys,
                              int64_t index_offset, void* stream, const int64_t* row_ids, SearchOpts opt) {
     const int D = ix->dim;
-    // device memory: the caller's stream, NULL = the null stream (ordered with the caller's
-    // default-stream work, e.g. PyTorch's); host memory: the caller's stream, or (NULL) the
-    // stream of the workspace this search takes, so concurrent host searches overlap
-    const bool own_stream = mem == VDB_MEM_HOST && !stream;
-    hipStream_t st = own_stream ? nullptr : (hipStream_t)stream;
     const int64_t N = ix->count;
     if (!opt.repass) {
         ix->n_searches++;
         ix->n_queries += B;
     }
 
-    // ---- sizes ----------------------------------------------------------------
-    // candidates beyond k: the certificate needs a gap of 2 eps between the k-th and the
-    // KP-th approximate score; bf16x3's bound grows with D (3D additions), so large D
-    // gets a wider margin (1M x 1536 uniform: KP = 32 left ~1.5% of queries uncertified)
+    // ---- the precision policy (stateful: VDB_PREC_AUTO's holds and re-pass bookkeeping) ----
     const bool auto_prec = ix->precision == VDB_PREC_AUTO;
     if (auto_prec && ix->h_totals && !opt.repass) {  // fallbacks of earlier device-memory searches (lagged)
         const unsigned long long seen = ix->h_totals[0];
@@ -1818,240 +1876,75 @@ static int32_t search_locked(vdb_index* ix, const float* queries, int32_t B, int
     // the "one plane" precisions (a wide certificate: KP = 128 for small k) and their re-pass
     const bool one_plane = prec_req == PREC_BF16 || prec_req == PREC_I8;
 
-    int margin_def = std::max(16, k / 4);
-    if ((prec_req == PREC_BF16X3 || prec_req == PREC_I8X3) && D >= 1024) margin_def = std::max(margin_def, 48);
-    // bf16 (hi plane only): eps ~ the rows' bf16 residual (~1.5e-3 relative on uniform data),
-    // ~30x bf16x3's: 1M x 768 uniform needs KP = 128 for k = 10 (KP = 64 left 26% of the
-    // queries uncertified; KP = 128: none of 2560)
-    if (one_plane) margin_def = std::max(16, std::min(std::max(112, k / 2), 256 - k));
-    // I8 (the 8-bit query's wider bound): KP = 256.  1M x 768 uniform, B = 64: KP = 128 left one
-    // query per batch uncertified; 256 none (profiles/r03_i8/c2_i8_kp*)
-    // -- except auto on small indexes (i8_narrow): at <= 512 K rows KP = 128 (one rank of an 8-way
-    // weak-scaled C2, 125 K rows x 512 queries: step 0.248 -> 0.207 ms, 0 fallbacks; 250 K: 0.181 ->
-    // 0.157; KP = 64 failed thousands of queries, profiles/r04_ab/rank*), widened for good at the
-    // first flagged query
-    // Rows of <= 128 dims (C6's 10M x 128): 0 fallbacks at KP = 128 even at 10 M rows, faster up to
-    // the 4-way shard (8-way 1.25 M x 512: 1.38 -> 1.56 M QPS; 4-way 2.5 M x 256: +4%) and slower
-    // at 10 M (262 -> 248 K: the KP = 128 scan's 106 KiB of LDS leaves no room beside it for the
-    // next batch's pilot, profiles/r04_ab/rank6m, c6m), hence 4 M
-    const bool i8_narrow = auto_prec && ix->i8_narrow != 0 && !ix->i8_wide &&
-                           (N <= kI8NarrowRows || (ix->Dp <= 128 && N <= kI8NarrowRowsShort));
-    if (prec_req == PREC_I8) margin_def = std::max(16, (i8_narrow ? 128 : 256) - k);
-    // I8Q (the 8-bit corpus's bound, as I8's): KP = 256
-    if (prec_req == PREC_I8Q) margin_def = std::max(16, 256 - k);
-    // a re-pass sub-search (host or device) takes KP = 128: its few queries are the ones whose
-    // rows sit closer together than the one-plane pass could separate, so they need the wider
-    // gap between the k-th and the KP-th candidate (C2 with 300 rows in a 3e-3 cosine band:
-    // BF16X3 at KP = 32 left every such query to the exact scan)
-    if (opt.repass) margin_def = std::max(margin_def, 128 - k);
-    const int margin = ix->margin >= 0 ? (int)ix->margin : margin_def;
-    int KP = std::max(32, next_pow2(k + margin));
-    const bool exact_all = ix->force_exact || k > kMaxApproxK || KP > 256;
-    if (KP > 256) KP = 256;
+    // ---- the plan (vdb_search_plan.h): pure arithmetic from here to the launches ----
     const int prec = prec_req;
-    const bool i8_pass = prec_is_i8(prec);  // vdb_scan8.hip
-    const int Gs = prec == PREC_FP32 ? ix->G : i8_pass ? ix->G / 4 : ix->G / 2;  // scan groups (8, 32 or 16 dims)
-    if (!i8_pass && !exact_all && N > 0 && !xs_ptr(ix)) {  // a split pass under AUTO + int8: the lazy copy
+    SearchShape sh{};
+    sh.B = B; sh.k = k; sh.D = D; sh.Dp = ix->Dp; sh.G = ix->G; sh.metric = ix->metric; sh.N = N; sh.n_cu = ix->n_cu;
+    sh.prec = prec; sh.host = mem == VDB_MEM_HOST; sh.gated = opt.gate != nullptr; sh.repass = opt.repass;
+    const SearchKnobs kn = search_knobs(ix, auto_prec && ix->i8_narrow != 0 && !ix->i8_wide);
+    const SearchKP kp = search_kp(sh, kn);
+    const int KP = kp.KP;
+    const bool exact_all = kp.exact_all;
+    if (!prec_is_i8(prec) && !exact_all && N > 0 && !xs_ptr(ix)) {  // a split pass under AUTO + int8: the lazy copy
         const int xr = ensure_xs(ix);
         if (xr) return xr;
     }
-    // fp32: vdb_scan.hip (variants); split-bf16 (bf16x3, bf16): vdb_scan2.hip
-    const bool split_pass = prec == PREC_BF16X3 || prec == PREC_BF16;
-    // The split pass's 128-query shape (vdb_scan2_kernel.h, q4): short rows whose query block
-    // fits LDS at 128 queries (D <= 128), KP = 128, batches of >= 256: half the query blocks, so
-    // each row range is re-read from L2 by half as many workgroups (C4: 8 -> 4 blocks)
-    const bool q4 = split_pass && !exact_all && !opt.gate && KP == 128 && B >= 256 && Gs <= 8 &&
-                    (ix->scan_q4 == 1 || (ix->scan_q4 < 0));
-    // The wide int8 pass (vdb_scan8w.hip): rows of 4 groups (D <= 128) and batches of more than 256
-    // (C4, and each rank of its row-sharded run): all queries of a 512-query block in one
-    // workgroup, the corpus staged once through LDS; one workgroup per CU, tiles dealt round-robin
-    const int64_t n_tiles_all = round_up(N, 32) / 32;
-    // ... and its long-row form (vdb_scan8wl.hip): the I8 cosine pass for 16..48 groups and up to
-    // 256 queries, all of them in one workgroup's registers, two waves per query tile for batches
-    // of <= 128 with rows of <= 1024 dims.  Auto (profiles/r06_wl3, r06_rl4): every batch for rows
-    // of <= 1024 dims (C2, B = 64: scan 0.142 -> 0.117 ms, 410 -> 432 K QPS; B = 2 / 32 / 128
-    // faster too); at 1536 dims batches of <= 16 and > 96 (C3: 420 -> 494 K; B = 32 even, 64
-    // slower).
-    const bool wide_long = i8_pass && !exact_all && !opt.gate && scan8wl_ok(prec, ix->metric, Gs, B) && N > 0 &&
-                           (ix->scan_wide == 1 ||
-                            (ix->scan_wide < 0 && N >= kWideMinRows && (Gs <= 32 || B <= 16 || B > 96)));
-    const bool wide8 = wide_long || (i8_pass && !exact_all && !opt.gate && scan8w_ok(Gs, B) && N > 0 &&
-                                     (ix->scan_wide == 1 ||
-                                      (ix->scan_wide < 0 && N >= kWideMinRows && (B > 256 || N <= kWideSplitMaxRows))));
-    const int n_seg8 = !wide8 ? 0
-                       : ix->n_wg_override > 0 ? (int)std::min<int64_t>(FIN_SEG_MAX, std::min<int64_t>(ix->n_wg_override, n_tiles_all))
-                                               : (int)std::min<int64_t>(FIN_SEG_MAX, round_up(std::min<int64_t>(ix->n_cu, n_tiles_all), 8));
-    // query rows per candidate-pass block: the int8 pass keeps 64 at KP = 256 (KW = 64 kept per
-    // workgroup, vdb_scan8_kernel.h), the split pass 32 there
-    const int QB = q4 ? 128 : i8_pass ? 64 : KP == 256 ? 32 : 64;
-    const int QB_pilot = i8_pass ? 64 : KP == 256 ? 32 : 64;  // the pilot's own query blocks (instantiations)
-    const int Bp = (int)round_up(B, 128);  // whole query super tiles (tiled layout)
-    const int n_qblocks = (B + QB - 1) / QB;
-    int variant = split_pass || i8_pass ? 0 : (int)ix->scan_variant;
-    if (!split_pass && !i8_pass && !scan_variant_ok(prec, variant, Gs)) variant = 0;  // e.g. PX=8 needs Dp % 128 == 0
-    const int64_t step_rows = i8_pass ? scan8_rows_per_step(prec, ix->metric)
-                              : split_pass ? scan2_rows_per_step(q4) : scan_rows_per_step(prec, variant);
-    const int64_t n_steps = std::max<int64_t>(1, round_up(N, step_rows) / step_rows);
-    // one 4-wave workgroup per CU (1 wave per SIMD, all of its 512 registers):
-    // measured faster than two per CU, whose top-k epilogues then overlap (profiles/)
-    int target = ix->n_wg_override > 0 ? (int)ix->n_wg_override : std::max(1, ix->n_cu / n_qblocks);
-    int spw = (int)std::max<int64_t>(1, (n_steps + target - 1) / target);
-    int n_wg = (int)((n_steps + spw - 1) / spw);
-    const int64_t mask_words = round_up(N, 32) / 32;
-    // Step end of the scan (vdb_scan.hip): short steps (Dp <= 128: C4's 10M x 128 runs 8 split
-    // groups per step, the epilogue ~half of it) gain from dropping the per-step workgroup barrier
-    // (C4 scan 7.58 -> 6.22 ms); long steps lose (C2 0.57 -> 0.65 ms, C3 2.62 -> 2.90 ms), measured.
-    // The int8 pass drops it at every length: a per-step barrier lines up the 4 waves' epilogues,
-    // so the CU's stream idles through all of them at once; flag-gated, one wave's epilogue runs
-    // under the others' loads (C2 366 -> 384 K QPS, C3 365 -> 401 K with its scan 0.576 -> 0.487 ms,
-    // profiles/r04_ab/sync, same box).
-    const int lockstep = ix->scan_sync == 0 ? (!i8_pass && ix->Dp > 128) : ix->scan_sync == 1;
+    const SearchGeometry g = search_geometry(sh, kn, kp, kernel_facts(sh, kn, kp));
+    const SearchPilot pilot = search_pilot(sh, kn, kp, g);
+    const SearchLayout lay = search_layout(sh, g, pilot);
+    const bool i8_pass = g.i8_pass, split_pass = g.split_pass, q4 = g.q4, wide_long = g.wide_long, wide8 = g.wide8;
+    const bool priv = g.priv, i8_refine = g.i8_refine, chk = g.chk, chk_l = g.chk_l;
+    const int Gs = g.Gs, n_seg8 = g.n_seg8, QB = g.QB, QB_pilot = g.QB_pilot, Bp = g.Bp, n_qblocks = g.n_qblocks;
+    const int variant = g.variant, n_wg = g.n_wg, spw = g.spw, lockstep = g.lockstep, n_wg8 = g.n_wg8;
+    const int fin_split = g.fin_split, R_rep = g.R_rep, n_pilot = pilot.n_pilot, pilot_rank = pilot.pilot_rank;
+    const int64_t n_steps = g.n_steps, mask_words = g.mask_words, gl_cap = g.gl_cap;
 
-    Workspace* w = acquire_ws(ix, st, own_stream);
-    if (own_stream) {
-        if (!w->own) {
-            const hipError_t e = hipStreamCreateWithFlags(&w->own, hipStreamNonBlocking);
-            if (e != hipSuccess) {
-                std::lock_guard<std::mutex> lg(ix->ws_mu);
-                w->busy = false;
-                return set_error(VDB_ERR_HIP, "workspace stream: %s", hipGetErrorString(e));
-            }
-        }
-        st = w->own;
-    }
-    struct Releaser {
-        vdb_index* ix; Workspace* w; hipStream_t st;
-        ~Releaser() { release_ws(ix, w, st); }
-    } rel{ix, w, st};
-
-    size_t bytes = 0;
-    bytes += (size_t)B * D * 4 + 256;                       // Qraw (host mode)
-    bytes += (size_t)(mask_words + 64) * 4 + 256;           // mask (host mode)
-    bytes += (size_t)Bp * (ix->Dp + 16 * QG_EXTRA) * 4 + 256;  // Qt (tiled fp32 or split, duplicated groups)
-    bytes += (size_t)Bp * 8 + 256;                          // qn64
-    bytes += (size_t)Bp * 24 + 256;                         // qconst: the finish's per-query constants
-    bytes += (size_t)Bp * KP * 8 + 512;                     // merged approx lists
-    bytes += (size_t)B * k * 20 + 768;                      // outputs (host mode)
-    bytes += (size_t)(B + 64) * 4 + 256;                    // flags
-    bytes += (size_t)Bp * 4 + 256;                          // gated fallback: workgroups done per query
-    // finish: optionally several workgroups per query share the exact rerank (tuning knob
-    // "finish_split"; measured at C2 bf16, B = 64: split 4 took the finish 24.5 -> 45.9 us,
-    // profiles/r02_ab, so the default is 1)
-    const int fin_split = (int)ix->finish_split;
-    bytes += fin_split > 1 ? (size_t)B * fin_split * (KP_MAX * 16 + 4) + 1024 : 0;
-    bytes += (size_t)Bp * 4 + 256;                          // shared thresholds
-    bytes += (size_t)Bp * (KP_MAX + PILOT_SLOTS) * 4 + 256;  // shared threshold slots + pilot slots
-    bytes += (size_t)Bp * 12 + 1024;                          // int8 pass: qmax, lsl, qerr [Bp]; qscal
-    // int8 L2 pass: the batch's integer accumulator start values (vdb_scan8.hip rstart8)
-    const bool rs8_on = i8_pass && !exact_all && ix->metric == 1;
-    bytes += rs8_on ? (size_t)round_up(N, 32) * 4 + 256 : 0;
-    const bool i8_refine = prec == PREC_I8 && ix->Xh &&  // the finish's I8 refinement
-                           (ix->i8_refine == 1 || (ix->i8_refine == -1 && ix->Dp >= kRefineMinDp));
-    bytes += i8_refine ? (size_t)Bp * (ix->Dp + 1) * 4 + 512 : 0;  // query residuals [Bp][Dp] + qerr2 [Bp]
-    const int R_rep = std::min(B, kRepassDev);                // device re-pass: gathered queries + results
-    bytes += mem == VDB_MEM_DEVICE ? (size_t)R_rep * (D * 4 + (size_t)k * 20) + 1024 : 0;
-    // the int8 pass's checksum: partial sums [2][n_wg8][Bp], expected values [Bp][2], L2 start sum
-    const bool chk = i8_pass && !exact_all && ix->scan_checksum && ix->d_csum && N > 0;
-    // the L sums of I8X3 too (scan_checksum 2): +5% on C4's scan over H alone (the xh plane, the
-    // query's hi plane and the start values; an L operand moves a score by at most the slack lsl)
-    const bool chk_l = chk && prec == PREC_I8X3 && ix->scan_checksum == 2;
-    const int n_wg8 = wide8 ? n_seg8 : (n_wg + 7) / 8 * 8;
-    bytes += wide8 ? (size_t)Bp * n_seg8 * 4 + 256 : 0;  // the wide pass's segment counts
-    bytes += chk ? ((size_t)2 * n_wg8 * Bp + (size_t)2 * Bp + 64) * 4 + 768 : 0;
-    const bool priv = !exact_all && !split_pass && !i8_pass && scan_priv(prec, variant, KP);
-    // global per-query candidate lists: at most 512 entries per workgroup and query
-    // (the largest LDS buffer of any variant; 4 x 64 for the wave-private one)
-    const int64_t gl_cap = exact_all ? 0 : wide8 ? (int64_t)n_seg8 * W8_CH
-                                              : (int64_t)((n_wg + 7) / 8 * 8) * 512;
-    bytes += (size_t)B * gl_cap * 8 + (size_t)Bp * 4 + 768;
-    // Pilot sample: 512 row tiles, more for large k (its bound then saves more insert work than
-    // the sample costs: C4, k = 100, 512 -> 4096 tiles: 89.5 K -> 96.4 K QPS, profiles/r02_ab),
-    // and at least 1/160 of the rows: the bound's global rank ~ r N / S sets how many entries
-    // each workgroup inserts (C6, 10 M rows, int8 pass: 512 -> 2048 tiles, scan 0.329 -> 0.259 ms,
-    // 200 K -> 250 K QPS; C2 / C3, 1 M rows: larger samples only add pilot time,
-    // profiles/r03_i8/pilot).
-    // Rows of 4 groups (D <= 128: the int8 pass's register-resident pilot, vdb_scan8.hip
-    // pilot8_g4) take twice the k-based sample, up to 8192 tiles where the rows are many (at most
-    // ~2.5% of them): C4 (k = 100) 4096 -> 8192, scan 2.32 -> 2.19 ms, 213 K -> 220 K QPS with
-    // the pilot at ~50 -> ~90 us (profiles/r05_ab/ab20)
-    const bool cheap_pilot = i8_pass && Gs == 4;
-    const int64_t pilot_cap = cheap_pilot ? std::max<int64_t>(4096, std::min<int64_t>(8192, N / (32 * 40))) : 4096;
-    const int64_t pilot_def = std::min<int64_t>(pilot_cap,
-                                                std::max<int64_t>((cheap_pilot ? 1024 : 512) * std::max(1, k / 12),
-                                                                  N / (32 * 160)));
-    const int n_pilot = opt.gate ? 0  // a gated re-pass sub-search: no pilot (few queries; its launches stay light)
-                                 : (int)std::min<int64_t>(ix->pilot_tiles >= 0 ? ix->pilot_tiles : pilot_def,
-                                                          round_up(N, 32) / 32);
-    // Rank of the pilot's bound among its sampled scores.  The KP-th best sample is a
-    // guaranteed lower bound of the global KP-th best but sits at global rank ~KP N / S (C2:
-    // ~2000), so the candidate pass inserts every score above that until its own buffers
-    // tighten (the warm-up: 140 us of a 680 us C2 scan without a pilot, ~65 us with one).
-    // Instead: the r-th best sample, r the smallest rank such that (1) the sample holds r of
-    // the global top k with probability < 1e-6 (Poisson(k S / N) tail; rows in no particular
-    // order), so T stays below a_k, and (2) T's expected global rank r N / S is >= 2 KP, so T
-    // mostly stays below a_KP too and the certificate's cut max(a_KP, T) is what it would be
-    // without a pilot (T near a_k failed bf16's wide certificate: C2 with 2048 tiles and rule
-    // (1) alone; the KP-based Poisson rule instead cost C2 bf16 7%, profiles/r02_ab).  C2: r = 5,
-    // T at rank ~300 instead of ~2000.  Exactness does not depend on it: rows dropped below the
-    // bound are covered by the certificate (acut >= T), which sends a query whose bound was too
-    // high to the exact path.
-    int pilot_rank = KP;
-    if (n_pilot > 0) {
-        const double S = (double)std::min<int64_t>((int64_t)n_pilot * 32, N);
-        const double x = (double)k * S / (double)N;
-        double term = std::exp(-x), cdf = term;
-        int r = 1;
-        while (1.0 - cdf >= 1e-6 && r < KP) {
-            term *= x / r;
-            cdf += term;
-            ++r;
-        }
-        const int r_min = (int)std::ceil(2.0 * KP * S / (double)N);
-        pilot_rank = std::min(std::max(r, r_min), KP);
-    }
-    if (ix->pilot_rank_override > 0) pilot_rank = (int)std::min<int64_t>(ix->pilot_rank_override, KP);
-    int rc = ws_reserve(w, bytes, st);
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+    int rc = ws_reserve(w, (size_t)lay.total, st);
     if (rc) return rc;
-    Carver c{w->dev};
-    float* Qraw = c.take<float>((size_t)B * D);
-    uint32_t* maskd = c.take<uint32_t>(mask_words + 64);
-    float* Qt = c.take<float>((size_t)Bp * (ix->Dp + 16 * QG_EXTRA));
-    double* qn64 = c.take<double>(Bp);
-    double* qconst = c.take<double>((size_t)Bp * 3);
+    char* const dev = w->dev;
+    auto at = [dev](int64_t off) { return off < 0 ? nullptr : dev + off; };  // (-1: no such buffer in this call)
+    float* Qraw = (float*)at(lay.Qraw);
+    uint32_t* maskd = (uint32_t*)at(lay.maskd);
+    float* Qt = (float*)at(lay.Qt);
+    double* qn64 = (double*)at(lay.qn64);
+    double* qconst = (double*)at(lay.qconst);
     // the finish's centring row and residual direction (the same conditions as its arguments below)
     const float* q_mu = i8_pass ? ix->d_mu : nullptr;
     const float* q_dir = (prec == PREC_BF16 || i8_pass) && ix->dir_set && !ix->no_dir_bound ? ix->d_dir : nullptr;
-    float* os = c.take<float>((size_t)B * k);
-    int64_t* oi = c.take<int64_t>((size_t)B * k);
-    double* ok = c.take<double>((size_t)B * k);
-    int* flags = c.take<int>(B + 64);
-    int* done = c.take<int>(Bp);
-    uint32_t* gthr = c.take<uint32_t>(Bp);
-    uint32_t* gslots = c.take<uint32_t>((size_t)Bp * (KP_MAX + PILOT_SLOTS));
+    float* os = (float*)at(lay.os);
+    int64_t* oi = (int64_t*)at(lay.oi);
+    double* ok = (double*)at(lay.ok);
+    int* flags = (int*)at(lay.flags);
+    int* done = (int*)at(lay.done);
+    uint32_t* gthr = (uint32_t*)at(lay.gthr);
+    uint32_t* gslots = (uint32_t*)at(lay.gslots);
     uint32_t* pslots = gslots + (size_t)Bp * KP_MAX;
-    float* gl_s = c.take<float>((size_t)B * gl_cap);
-    uint32_t* gl_i = c.take<uint32_t>((size_t)B * gl_cap);
-    uint32_t* gl_cnt = c.take<uint32_t>(Bp);
-    double* fx_ek = fin_split > 1 ? c.take<double>((size_t)B * fin_split * KP_MAX) : nullptr;
-    uint32_t* fx_ck = fin_split > 1 ? c.take<uint32_t>((size_t)B * fin_split * KP_MAX) : nullptr;
-    uint32_t* fx_cr = fin_split > 1 ? c.take<uint32_t>((size_t)B * fin_split * KP_MAX) : nullptr;
-    int* fx_n = fin_split > 1 ? c.take<int>((size_t)B * fin_split) : nullptr;
-    float* q8max = c.take<float>(Bp);
-    float* q8lsl = c.take<float>(Bp);
-    float* q8err = c.take<float>(Bp);
-    float* q8scal = c.take<float>(64);
-    float* q8res = i8_refine ? c.take<float>((size_t)Bp * ix->Dp) : nullptr;
-    float* q8err2 = i8_refine ? c.take<float>(Bp) : nullptr;
-    uint32_t* chkp = chk ? c.take<uint32_t>((size_t)2 * n_wg8 * Bp) : nullptr;
-    uint32_t* segc = wide8 ? c.take<uint32_t>((size_t)Bp * n_seg8) : nullptr;
-    uint32_t* chkr = chk && ix->metric == 1 ? c.take<uint32_t>(64) : nullptr;
-    int* rs8 = rs8_on ? c.take<int>((size_t)round_up(N, 32)) : nullptr;
-    // (the pilot writes the checksum's expectations when it runs; else the finish computes them)
-    uint32_t* chke = chk && n_pilot > 0 ? c.take<uint32_t>((size_t)2 * Bp) : nullptr;
-    float* rep_q = mem == VDB_MEM_DEVICE ? c.take<float>((size_t)R_rep * D) : nullptr;
-    float* rep_s = mem == VDB_MEM_DEVICE ? c.take<float>((size_t)R_rep * k) : nullptr;
-    int64_t* rep_i = mem == VDB_MEM_DEVICE ? c.take<int64_t>((size_t)R_rep * k) : nullptr;
-    double* rep_k = mem == VDB_MEM_DEVICE ? c.take<double>((size_t)R_rep * k) : nullptr;
+    float* gl_s = (float*)at(lay.gl_s);
+    uint32_t* gl_i = (uint32_t*)at(lay.gl_i);
+    uint32_t* gl_cnt = (uint32_t*)at(lay.gl_cnt);
+    double* fx_ek = (double*)at(lay.fx_ek);
+    uint32_t* fx_ck = (uint32_t*)at(lay.fx_ck);
+    uint32_t* fx_cr = (uint32_t*)at(lay.fx_cr);
+    int* fx_n = (int*)at(lay.fx_n);
+    float* q8max = (float*)at(lay.q8max);
+    float* q8lsl = (float*)at(lay.q8lsl);
+    float* q8err = (float*)at(lay.q8err);
+    float* q8scal = (float*)at(lay.q8scal);
+    float* q8res = (float*)at(lay.q8res);
+    float* q8err2 = (float*)at(lay.q8err2);
+    uint32_t* chkp = (uint32_t*)at(lay.chkp);
+    uint32_t* segc = (uint32_t*)at(lay.segc);
+    uint32_t* chkr = (uint32_t*)at(lay.chkr);
+    int* rs8 = (int*)at(lay.rs8);
+    uint32_t* chke = (uint32_t*)at(lay.chke);
+    float* rep_q = (float*)at(lay.rep_q);
+    float* rep_s = (float*)at(lay.rep_s);
+    int64_t* rep_i = (int64_t*)at(lay.rep_i);
+    double* rep_k = (double*)at(lay.rep_k);
 
     const float* Qd = queries;
     const uint32_t* md = row_mask;
@@ -2236,7 +2129,7 @@ static int32_t search_locked(vdb_index* ix, const float* queries, int32_t B, int
             // launched gated on the device's flag count (nothing runs when no query was
             // flagged), so the call returns with the whole search queued.
             if (ix->no_fallback && mem == VDB_MEM_DEVICE) return VDB_OK;
-            if (!ix->no_fallback && mem == VDB_MEM_DEVICE && exact_bytes(ix, B, k, true) <= kGatedExactBytes) {
+            if (!ix->no_fallback && mem == VDB_MEM_DEVICE && gated_exact_bytes(ix, B, k) <= kGatedExactBytes) {
                 {
                     std::lock_guard<std::mutex> lg(ix->ws_mu);  // lazily, once (concurrent searches)
                     if (!ix->d_totals) {
@@ -2430,24 +2323,10 @@ int32_t vdb_index_search_rows(vdb_index* ix, const float* queries, int32_t B, in
     }
     // as a search: the caller's stream (device memory: NULL = the null stream), or for a
     // host-memory call without one the stream of the workspace it takes
-    const bool own_stream = mem == VDB_MEM_HOST && !stream;
-    hipStream_t st = own_stream ? nullptr : (hipStream_t)stream;
-    Workspace* w = acquire_ws(ix, st, own_stream);
-    if (own_stream) {
-        if (!w->own) {
-            const hipError_t e = hipStreamCreateWithFlags(&w->own, hipStreamNonBlocking);
-            if (e != hipSuccess) {
-                std::lock_guard<std::mutex> lg(ix->ws_mu);
-                w->busy = false;
-                return set_error(VDB_ERR_HIP, "workspace stream: %s", hipGetErrorString(e));
-            }
-        }
-        st = w->own;
-    }
-    struct Releaser {
-        vdb_index* ix; Workspace* w; hipStream_t st;
-        ~Releaser() { release_ws(ix, w, st); }
-    } rel{ix, w, st};
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
 
     const bool host = mem == VDB_MEM_HOST;
     const int KE = subset_ke(k);
@@ -2465,14 +2344,13 @@ int32_t vdb_index_search_rows(vdb_index* ix, const float* queries, int32_t B, in
     a.out_i = out_indices;
     a.out_k = out_keys;
     if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
-        rc = ws_host_io(w, (size_t)(sc.in_bytes + sc.out_bytes));
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+            std::memcpy(h + (sc.offs - sc.in0), list_offsets, ((size_t)n_lists + 1) * 8);
+            if (n_ids > 0) std::memcpy(h + (sc.rows - sc.in0), list_rows, (size_t)n_ids * 8);
+            if (query_list) std::memcpy(h + (sc.qlist - sc.in0), query_list, (size_t)B * 4);
+        });
         if (rc) return rc;
-        char* h = w->host_io;
-        std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
-        std::memcpy(h + (sc.offs - sc.in0), list_offsets, ((size_t)n_lists + 1) * 8);
-        if (n_ids > 0) std::memcpy(h + (sc.rows - sc.in0), list_rows, (size_t)n_ids * 8);
-        if (query_list) std::memcpy(h + (sc.qlist - sc.in0), query_list, (size_t)B * 4);
-        HIP_TRY(hipMemcpyAsync(dev + sc.in0, h, (size_t)sc.in_bytes, hipMemcpyHostToDevice, st));
         a.Q = reinterpret_cast<const float*>(dev + sc.q);
         a.offs = reinterpret_cast<const int64_t*>(dev + sc.offs);
         a.rows = reinterpret_cast<const int64_t*>(dev + sc.rows);
@@ -2509,9 +2387,9 @@ int32_t vdb_index_search_rows(vdb_index* ix, const float* queries, int32_t B, in
         HIP_TRY(launch_subset_search(ix->metric, a, B, n_seg, st));
     }
     if (host) {
-        char* r = w->host_io + sc.in_bytes;
-        HIP_TRY(hipMemcpyAsync(r, dev + sc.out0, (size_t)sc.out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
         std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
         std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
         if (out_keys) std::memcpy(out_keys, r + (sc.out_k - sc.out0), (size_t)B * k * 8);
@@ -2554,24 +2432,10 @@ int32_t vdb_index_search_range(vdb_index* ix, const float* queries, int32_t B, c
     const int64_t N = ix->count;
     // as vdb_index_search_rows: the caller's stream (device memory: NULL = the null stream), or for
     // a host-memory call without one the stream of the workspace it takes
-    const bool own_stream = host && !stream;
-    hipStream_t st = own_stream ? nullptr : (hipStream_t)stream;
-    Workspace* w = acquire_ws(ix, st, own_stream);
-    if (own_stream) {
-        if (!w->own) {
-            const hipError_t e = hipStreamCreateWithFlags(&w->own, hipStreamNonBlocking);
-            if (e != hipSuccess) {
-                std::lock_guard<std::mutex> lg(ix->ws_mu);
-                w->busy = false;
-                return set_error(VDB_ERR_HIP, "workspace stream: %s", hipGetErrorString(e));
-            }
-        }
-        st = w->own;
-    }
-    struct Releaser {
-        vdb_index* ix; Workspace* w; hipStream_t st;
-        ~Releaser() { release_ws(ix, w, st); }
-    } rel{ix, w, st};
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
 
     const bool masked = row_mask != nullptr && N > 0;
     const RangeScratch sc = range_scratch(B, D, ix->Dp, N, cap, host, masked, out_keys != nullptr);
@@ -2587,13 +2451,12 @@ int32_t vdb_index_search_range(vdb_index* ix, const float* queries, int32_t B, c
     a.out_s = out_scores;
     a.out_k = out_keys;
     if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
-        rc = ws_host_io(w, (size_t)(sc.in_bytes + sc.out_bytes));
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+            std::memcpy(h + (sc.thr - sc.in0), thresholds, (size_t)B * 8);
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.n_words * 4);
+        });
         if (rc) return rc;
-        char* h = w->host_io;
-        std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
-        std::memcpy(h + (sc.thr - sc.in0), thresholds, (size_t)B * 8);
-        if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.n_words * 4);
-        HIP_TRY(hipMemcpyAsync(dev + sc.in0, h, (size_t)sc.in_bytes, hipMemcpyHostToDevice, st));
         a.Q = reinterpret_cast<const float*>(dev + sc.q);
         a.thr = reinterpret_cast<const double*>(dev + sc.thr);
         a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
@@ -2627,9 +2490,9 @@ int32_t vdb_index_search_range(vdb_index* ix, const float* queries, int32_t B, c
             HIP_TRY(launch_range_block(ix->metric, a, b0, std::min(sc.block, B - b0), st));
     }
     if (host) {
-        char* r = w->host_io + sc.in_bytes;
-        HIP_TRY(hipMemcpyAsync(r, dev + sc.out0, (size_t)sc.out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
         std::memcpy(out_counts, r + (sc.out_c - sc.out0), (size_t)B * 8);
         if (cap > 0) {
             std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * cap * 8);
@@ -2688,12 +2551,7 @@ int32_t vdb_index_set_groups(vdb_index* ix, const int32_t* groups, int64_t n, in
     if (n > 0) {
         if (mem == VDB_MEM_DEVICE) {
             // the ids may still be being written on the caller's stream: the copy starts after that work
-            hipEvent_t ready = nullptr;
-            HIP_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-            hipError_t e = hipEventRecord(ready, (hipStream_t)stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(st, ready, 0);
-            (void)hipEventDestroy(ready);
-            HIP_TRY(e);
+            HIP_TRY(order_after_caller(st, stream));
         }
         HIP_TRY(hipMemcpyAsync(ix->groups, groups, (size_t)n * sizeof(int32_t),
                                mem == VDB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
@@ -2738,24 +2596,10 @@ int32_t vdb_index_search_groups(vdb_index* ix, const float* queries, int32_t B, 
         return set_error(VDB_ERR_INVALID, "no group column is attached (vdb_index_set_groups; add, remove and clear drop it)");
     // as vdb_index_search_rows: the caller's stream (device memory: NULL = the null stream), or for
     // a host-memory call without one the stream of the workspace it takes
-    const bool own_stream = host && !stream;
-    hipStream_t st = own_stream ? nullptr : (hipStream_t)stream;
-    Workspace* w = acquire_ws(ix, st, own_stream);
-    if (own_stream) {
-        if (!w->own) {
-            const hipError_t e = hipStreamCreateWithFlags(&w->own, hipStreamNonBlocking);
-            if (e != hipSuccess) {
-                std::lock_guard<std::mutex> lg(ix->ws_mu);
-                w->busy = false;
-                return set_error(VDB_ERR_HIP, "workspace stream: %s", hipGetErrorString(e));
-            }
-        }
-        st = w->own;
-    }
-    struct Releaser {
-        vdb_index* ix; Workspace* w; hipStream_t st;
-        ~Releaser() { release_ws(ix, w, st); }
-    } rel{ix, w, st};
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
 
     const bool masked = row_mask != nullptr && N > 0;
     const bool force = ix->group_force_exact != 0;
@@ -2772,12 +2616,11 @@ int32_t vdb_index_search_groups(vdb_index* ix, const float* queries, int32_t B, 
     int32_t* out_g = out_groups;
     double* out_k = out_keys;
     if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
-        rc = ws_host_io(w, (size_t)(sc.in_bytes + sc.out_bytes));
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+        });
         if (rc) return rc;
-        char* h = w->host_io;
-        std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
-        if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
-        HIP_TRY(hipMemcpyAsync(dev + sc.in0, h, (size_t)sc.in_bytes, hipMemcpyHostToDevice, st));
         Qd = reinterpret_cast<const float*>(dev + sc.q);
         cm = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
         out_s = reinterpret_cast<float*>(dev + sc.out_s);
@@ -2844,9 +2687,9 @@ int32_t vdb_index_search_groups(vdb_index* ix, const float* queries, int32_t B, 
         HIP_TRY(launch_group_exact(ix->metric, ea, B, n_seg, st));
     }
     if (host) {
-        char* r = w->host_io + sc.in_bytes;
-        HIP_TRY(hipMemcpyAsync(r, dev + sc.out0, (size_t)sc.out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
         std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
         std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
         std::memcpy(out_groups, r + (sc.out_g - sc.out0), (size_t)B * k * 4);

@@ -1,7 +1,11 @@
-// vdb_internal.h — host-side launchers for the kernels in vdb_kernels.hip.
+// vdb_internal.h — host-side launchers for the kernels (one section per .hip file).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+// PREC_*, QG_EXTRA, W8_CH, KP_MAX, PILOT_SLOTS and the other plain constants the main search's host
+// arithmetic shares with the kernels
+#include "vdb_search_plan.h"
 
 namespace vdb {
 
@@ -9,29 +13,7 @@ namespace vdb {
 constexpr int TILE_ROWS = 32;      // rows per row tile
 constexpr int GROUP_DIMS = 8;      // dims per (tile, group) block
 constexpr int BLOCK_FLOATS = 256;  // floats per (tile, group) block = 1 KiB
-constexpr int QG_EXTRA = 8;        // duplicated leading dim-groups at the end of each query tile
 constexpr int ROW_ALIGN = 1024;    // corpus capacity granule (>= rows per scan step of any variant)
-
-// Candidate-pass arithmetic (vdb.h VDB_PREC_*):
-//   PREC_FP32   fp32 corpus tiles, v_mfma_f32_32x32x2_f32 (8-dim groups, 4 KiB per super-tile group)
-//   PREC_BF16X3 split-bf16 corpus (x = hi + lo + O(2^-16 x)), three v_mfma_f32_32x32x16_bf16 per
-//               16-dim group: hi*hi + hi*lo + lo*hi (8 KiB per super-tile group: [plane][sub tile])
-constexpr int PREC_FP32 = 0;
-constexpr int PREC_BF16X3 = 1;
-//   PREC_BF16   the hi plane of the split copy only (x ~ bf16(x), half the bytes), query split:
-//               x.q ~ xh.qh + xh.ql, two v_mfma_f32_32x32x16_bf16 per 16-dim group; bounded by the
-//               index's largest row residual |x - bf16(x)| (pack_rows)
-constexpr int PREC_BF16 = 2;
-//   PREC_I8     int8 copy of the centred rows (vdb_scan8_kernel.h): x ~ s_x xh (1 byte per element),
-//               query s_q qh (8 bits): one v_mfma_i32_32x32x32_i8 per 32-dim group
-//   PREC_I8X3   both planes of the int8 copy, x ~ s_x (xh + xl/256), query 16 bits: three per group
-//   PREC_I8Q    the xh plane (8 bits, 1 byte per element) against the 16-bit query: xh.qh + xh.ql /
-//               256, two per group (L2, 16 < k <= 100: C4)
-constexpr int PREC_I8 = 3;
-constexpr int PREC_I8X3 = 4;
-constexpr int PREC_I8Q = 5;
-constexpr int N_PREC = 6;
-inline bool prec_is_i8(int p) { return p == PREC_I8 || p == PREC_I8X3 || p == PREC_I8Q; }
 
 // Per-index constants of the int8 pass (vdb_api.cpp): the quantisation step s_x of the centred
 // rows, max |s_x xh| and max |s_x xl / 256| over the rows (row norms), max |x|^2 / 2 (L2 start)
@@ -64,9 +46,8 @@ hipError_t launch_pilot8(int prec, int metric, const float* Xq, const float* rin
                          int n_sample, uint32_t* pslots, hipStream_t st, const uint32_t* csum = nullptr,
                          uint32_t* chke = nullptr, bool wide = false);
 int scan8_rows_per_step(int prec, int metric);  // (64 queries per block of the int8 pass)
-// the wide int8 pass (vdb_scan8w.hip): rows of 4 groups, batches of more than 256; W8_CH slots per
-// (workgroup, query) segment of the candidate lists
-constexpr int W8_CH = 32;
+// the wide int8 pass (vdb_scan8w.hip): rows of 4 groups, batches of more than 256; W8_CH
+// (vdb_search_plan.h) slots per (workgroup, query) segment of the candidate lists
 bool scan8w_ok(int G8, int B);
 // its long-row form (vdb_scan8wl.hip): I8 cosine, 16 / 24 / 32 / 48 groups, 129..256 queries
 bool scan8wl_ok(int prec, int metric, int G8, int B);
@@ -163,11 +144,7 @@ hipError_t launch_update_colsum8(const float* Xq, const int64_t* ids, int64_t n,
 // The index's rows -> row-major fp32 [n][D] (export for persistence).
 hipError_t launch_unpack_rows(const float* X, int G, int D, int64_t row0, int64_t n, float* dst, hipStream_t st);
 
-// gthr[B]: per-query shared threshold (order-preserving score key, 0 = none) and
-// gslots[B][KP_MAX]: per-query slots of published workgroup bests; both zeroed by
-// prep_queries (see the publish step of scan_topk_kernel).
-constexpr int KP_MAX = 256;
-constexpr int PILOT_SLOTS = 256;  // pilot bound slots per query
+// gthr[B], gslots[B][KP_MAX] and the PILOT_SLOTS pilot slots per query: vdb_search_plan.h.
 // pslots layout: slot-major, [PILOT_SLOTS][B] (a pilot wave's 32 queries of one tile -> one 128-byte
 // segment per atomic instruction; query-major, each went to 32 cache lines: the guide's
 // 17x-slower scattered-atomic shape, ~100 us of C4's 219 us pilot)
