@@ -409,9 +409,12 @@ int32_t vdb_similarity_matrix(const float* corpus, int64_t n, int32_t dim,
 int32_t vdb_normalize_rows(const float* in, int64_t n, int32_t dim, float* out, void* stream);
 /* `fast_top_k_indices` / `mx.argsort(-scores)[:k]` (mlx_optimized.py:90-108,
  * optimized_vector_store.py:176-183) over `rows` score rows of length n (device
- * memory): the k best per row, largest first (largest = 1) or smallest first, ties to
- * the lower index, NaN last.  out_indices [rows, k] int64, out_values NULL or
- * [rows, k] fp32.  1 <= k <= min(n, 1024). */
+ * memory): the k best per row, largest first (largest = 1) or smallest first.  The
+ * key is s when largest, otherwise -s, with NaN mapped to -inf; order is key
+ * descending, index ascending.  So ties go to the lower index (-0.0 and +0.0 tie),
+ * and NaN ties with the worst infinity and is ordered against it by index.
+ * out_indices [rows, k] int64; out_values NULL or [rows, k] fp32, the raw scores at
+ * the returned indices.  1 <= k <= min(n, 1024). */
 int32_t vdb_topk_scores(const float* scores, int32_t rows, int64_t n, int32_t k, int32_t largest,
                         int64_t* out_indices, float* out_values, void* stream);
 

@@ -121,8 +121,9 @@ hipError_t launch_similarity_matrix(const float* X, int64_t N, int D, const floa
 }
 
 // ---- row normalisation ----------------------------------------------------------------------
-__global__ void __launch_bounds__(256) normalize_kernel(const float* __restrict__ in, int64_t n, int D,
-                                                        float* __restrict__ out) {
+// in == out is allowed (include/vdb.h), so neither pointer is __restrict__: a wave owns its row,
+// finishes the sum of squares before its first store, and each lane rewrites only what it read.
+__global__ void __launch_bounds__(256) normalize_kernel(const float* in, int64_t n, int D, float* out) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n) return;

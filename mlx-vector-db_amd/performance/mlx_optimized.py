@@ -32,6 +32,8 @@ from service import _vdb
 
 logger = logging.getLogger("mlx_vector_db.optimized")
 
+TOPK_MAX_K = 1024  # vdb_topk_scores: 1 <= k <= min(n, 1024) (include/vdb.h)
+
 
 def _torch():
     import torch
@@ -110,6 +112,13 @@ def fast_top_k_indices(scores, k: int):
     kk = min(int(k), s.shape[0])
     if k <= 0 or kk == 0:
         return _out(torch.zeros(0, dtype=torch.int32, device=s.device), t)
+    if kk > TOPK_MAX_K:
+        # vdb_topk_scores serves k <= 1024; the reference's argsort(-s)[:k] has no cap.  Past it:
+        # a stable descending device sort under the operator's rule (NaN keyed as -inf, ties to the
+        # lower index); nothing goes to the host.
+        key = torch.where(torch.isnan(s), torch.full_like(s, float("-inf")), s)
+        idx = torch.sort(key, descending=True, stable=True).indices[:kk]
+        return _out(idx.to(torch.int32), t)
     idx = torch.empty(kk, dtype=torch.int64, device=s.device)
     _vdb.topk_scores_device(s.data_ptr(), 1, s.shape[0], kk, True, idx.data_ptr(), 0, _stream(s))
     return _out(idx.to(torch.int32), t)

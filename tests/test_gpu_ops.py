@@ -73,6 +73,32 @@ def test_topk_and_searches(mo):
     assert "optimized_batch_similarity_search" in mo.performance_monitor.get_stats()
 
 
+def test_topk_above_the_operator_cap(mo, monkeypatch):
+    """fast_top_k_indices answers for any k <= len(s), as the reference's argsort(-s)[:k] does:
+    past vdb_topk_scores' k <= 1024, the same rule (NaN as -inf, ties to the lower index), on
+    the device (no tensor goes to the host)."""
+    import torch
+    rng = np.random.default_rng(54)
+    s = (np.round(rng.standard_normal(5000) * 4) / 4).astype(np.float32)   # ~30 levels: ties throughout
+    s[[17, 4000]] = np.nan
+    key = np.where(np.isnan(s), -np.inf, s).astype(np.float32)
+    assert np.unique(key).size < 100
+    for k in (1025, 5000):
+        ref = ref_cpu.reference_topk_indices(key, k)
+        assert mo.fast_top_k_indices(s, k).tolist() == ref.tolist()
+    assert mo.fast_top_k_indices(s, 6000).size == 5000
+    sd = torch.from_numpy(s).cuda()
+    copies = []
+    real_cpu = torch.Tensor.cpu
+    monkeypatch.setattr(torch.Tensor, "cpu", lambda self, *a, **kw: copies.append(1) or real_cpu(self, *a, **kw))
+    outs = [mo.fast_top_k_indices(sd, k) for k in (1025, 5000)]
+    torch.cuda.synchronize()
+    assert copies == []
+    monkeypatch.setattr(torch.Tensor, "cpu", real_cpu)
+    for k, o in zip((1025, 5000), outs):
+        assert o.is_cuda and o.cpu().tolist() == ref_cpu.reference_topk_indices(key, k).tolist()
+
+
 def test_device_tensors_stay_on_device(mo):
     import torch
     rng = np.random.default_rng(52)
