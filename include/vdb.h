@@ -379,6 +379,56 @@ int32_t vdb_index_search_groups(vdb_index* idx, const float* queries, int32_t n_
                                 float* out_scores, int64_t* out_indices, int32_t* out_groups, double* out_keys,
                                 int64_t index_offset, void* stream);
 
+/* --- MMR search: k relevant and mutually diverse rows -----------------------------
+ * Replaces: nothing the reference has.  Its RAG pipeline cuts documents into chunks that overlap
+ * by 50 characters and fills a fixed context with the best chunks
+ * (integrations/mlx_lm_pipeline.py:646-756), so near-copies of one paragraph fill the context.
+ * Maximal marginal relevance (Carbonell & Goldstein) is the usual answer; without this call a user
+ * runs search(fetch_k), pulls the rows to the host one by one and builds a fetch_k x fetch_k
+ * similarity matrix in numpy per query, and a device-memory caller cannot do it at all.
+ *
+ *   k            1..200 rows per query
+ *   fetch_k      k..200 candidates per query (the most the certified fast path returns)
+ *   lambda       host fp64, finite, in [0, 1]: 1 = relevance only, 0 = diversity only
+ *   out_scores / out_indices / out_keys: [n_queries, k] in pick order; out_keys may be NULL
+ *   out_mmr      NULL, or [n_queries, k] fp64: the value each pick won with
+ *   queries, row_mask, mem, index_offset, stream: as vdb_index_search; all pointers of one memory
+ *                kind.  n_queries == 0 is VDB_OK.
+ * Candidates: query b's list c_0 .. c_{n-1} is what vdb_index_search(k = fetch_k, row_mask)
+ * returns, the best n = min(fetch_k, eligible rows) rows by (canonical key desc, row asc); rel_i is
+ * the canonical fp64 key of (q_b, c_i).  Pair similarity: S[i][j] is the canonical fp64 key of the
+ * pair (stored row c_i taken as the query, stored row c_j), the same metric and operation order as
+ * any key.  Both terms are in KEY units for both metrics: cosine similarity, and MINUS THE SQUARED
+ * L2 distance for euclidean.  Euclidean stays in squared units on purpose: the formula then holds
+ * no square root whose rounding an oracle would have to match (so lambda weighs squared distances
+ * there).  S is bitwise symmetric for finite rows (products and the norm product commute,
+ * (x-q)^2 == (q-x)^2), so each pair is computed once.
+ * Selection, all fp64 with separate multiply and subtract: slot 0 is position 0 with mmr_0 =
+ * lambda * rel_0 and pen_i = S[i][0]; every further slot computes v_i = lambda * rel_i -
+ * (1.0 - lambda) * pen_i over the unpicked positions, picks the greatest (a tie goes to the lower
+ * position: the better key, then the lower row id), sets mmr_t = v_pick and pen_i = (S[i][pick] >
+ * pen_i) ? S[i][pick] : pen_i; it stops after min(k, n) picks.  out_indices = row id +
+ * index_offset, out_keys = rel, out_scores = rel rounded as a search rounds it, out_mmr = mmr_t;
+ * slots past min(k, n) hold index -1 / score 0 / key -inf / mmr -inf.
+ * lambda == 1 returns, byte for byte, the first k slots of vdb_index_search(k).  The result is the
+ * same bytes for every precision setting and both memory kinds: the inner search is certified
+ * exact, and everything after it reads only the fp32 rows and their canonical norms.
+ * How: the inner search fetches the lists into scratch; per block of max(1, 64 MiB / (fetch_k^2 *
+ * 8)) queries one kernel scores the pairs i < j of each list (one wave per position i and batch of
+ * four positions j) and one kernel selects (one wave per query).
+ * Errors: k outside [1, 200], fetch_k outside [k, 200], lambda outside [0, 1] or NaN, n_queries
+ * < 0, a NULL queries / out_scores / out_indices -> VDB_ERR_INVALID; host-memory queries with NaN /
+ * Inf -> VDB_ERR_NONFINITE, before anything is launched.  Device-memory calls are stream-ordered
+ * and read nothing back.  Takes the index's shared lock and a per-search workspace, as
+ * vdb_index_search_groups does.  An empty index gives every slot "no result".  Stats (cumulative,
+ * successful calls): "mmr_searches", "mmr_queries"; "searches" / "queries" move once per call
+ * through the inner search. */
+int32_t vdb_index_search_mmr(vdb_index* idx, const float* queries, int32_t n_queries,
+                             int32_t k, int32_t fetch_k, double lambda,
+                             const uint32_t* row_mask, int32_t mem,
+                             float* out_scores, int64_t* out_indices, double* out_keys,
+                             double* out_mmr, int64_t index_offset, void* stream);
+
 /* --- multi-GPU merge -----------------------------------------------------------
  * Merge per-shard top-k lists (all device memory, already all-gathered):
  *   keys [n_lists, n_queries, k_in] fp64 ranking keys (higher first),

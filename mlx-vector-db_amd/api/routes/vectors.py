@@ -70,6 +70,15 @@ class VectorQuery(BaseModel):
     filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
 
 
+class VectorMMRQuery(VectorQuery):
+    """/vectors/query's body plus the two MMR settings: ``k`` rows picked from the best ``fetch_k``
+    (null: min(200, max(4 k, 20))), each maximising ``lambda_mult`` * relevance - (1 - ``lambda_mult``)
+    * its greatest similarity to a row picked before.  The store checks the limits (k and fetch_k at
+    most 200, fetch_k >= k, lambda_mult in [0, 1]); a value outside them is a 400."""
+    fetch_k: Optional[int] = Field(default=None, description="Candidates the rows are picked from")
+    lambda_mult: float = Field(default=0.5, description="1 = relevance only, 0 = diversity only")
+
+
 class VectorRangeQuery(BaseModel):
     """Every stored row within ``threshold`` of the query: a minimum similarity for a cosine
     store, a maximum distance for a euclidean one."""
@@ -382,6 +391,35 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in grouped query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Grouped query failed: {e}")
+
+    @router.post("/mmr_query", response_model=VectorQueryResponse)
+    async def mmr_query_vectors(request: VectorMMRQuery, api_key: str = Depends(auth)):
+        """``k`` relevant and mutually diverse rows (maximal marginal relevance) in pick order, in
+        /vectors/query's format.  A bad request (empty query, k / fetch_k / lambda_mult outside their
+        limits, dimension mismatch: the store's ValueError) is a 400, an unsupported store a 501,
+        anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if not request.query:
+                raise HTTPException(status_code=400, detail="Query vector required")
+            loop = asyncio.get_running_loop()
+            indices, scores, metas = await loop.run_in_executor(
+                mgr._executor, lambda: store.mmr_query(request.query, k=request.k, fetch_k=request.fetch_k,
+                                                       lambda_mult=request.lambda_mult,
+                                                       filter_metadata=request.filter_metadata))
+            return VectorQueryResponse(results=format_query_results(store.config.metric, indices, scores, metas),
+                                       query_time_ms=(time.time() - t0) * 1000,
+                                       total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"MMR query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"MMR query failed: {e}")
+        except Exception as e:
+            logger.error("Error in MMR query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"MMR query failed: {e}")
 
     @router.post("/batch_query", response_model=BatchQueryResponse)
     async def batch_query_vectors(request: BatchQueryRequest, api_key: str = Depends(auth)):

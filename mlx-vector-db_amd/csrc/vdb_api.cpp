@@ -27,6 +27,7 @@
 #include "vdb_subset_plan.h"
 #include "vdb_range_plan.h"
 #include "vdb_group_plan.h"
+#include "vdb_mmr_plan.h"
 #include "vdb_search_plan.h"
 #include "vdb_internal.h"
 
@@ -248,6 +249,8 @@ struct vdb_index {
     unsigned long long* d_group_fb = nullptr;
     int64_t group_fetch = 0;        // knob: rows the inner search fetches (0 = auto, vdb_group_plan.h)
     int64_t group_force_exact = 0;  // knob: every query takes the exact fallback (tests, A/B)
+    // vdb_index_search_mmr: calls and queries (successful calls)
+    std::atomic<int64_t> n_mmr_searches{0}, n_mmr_queries{0};
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -1153,6 +1156,8 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "group_sets") *value = ix->n_group_sets.load();
     else if (n == "group_searches") *value = ix->n_group_searches.load();
     else if (n == "group_queries") *value = ix->n_group_queries.load();
+    else if (n == "mmr_searches") *value = ix->n_mmr_searches.load();
+    else if (n == "mmr_queries") *value = ix->n_mmr_queries.load();
     else if (n == "group_fallback_queries") {  // counted by the select kernel: after the searches queued so far
         unsigned long long fb = 0;
         if (ix->d_group_fb) {
@@ -2701,6 +2706,112 @@ int32_t vdb_index_search_groups(vdb_index* ix, const float* queries, int32_t B, 
     }
     ix->n_group_searches++;
     ix->n_group_queries += B;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_mmr(vdb_index* ix, const float* queries, int32_t B, int32_t k, int32_t fetch_k, double lambda,
+                             const uint32_t* row_mask, int32_t mem, float* out_scores, int64_t* out_indices,
+                             double* out_keys, double* out_mmr, int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    // everything checked before any launch
+    switch (mmr_validate(B, k, fetch_k, lambda, queries != nullptr || B == 0, out_scores != nullptr || B == 0,
+                         out_indices != nullptr || B == 0, mem)) {
+        case kMmrBadQueries: return set_error(VDB_ERR_INVALID, "n_queries must be >= 0, got %d", B);
+        case kMmrBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", kMmrMaxK, k);
+        case kMmrBadFetch:
+            return set_error(VDB_ERR_INVALID, "fetch_k must be in [k, %d], got fetch_k=%d k=%d", kMmrMaxFetch, fetch_k, k);
+        case kMmrBadLambda: return set_error(VDB_ERR_INVALID, "lambda must be in [0, 1], got %g", lambda);
+        case kMmrNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/output pointer");
+        case kMmrBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+        default: break;
+    }
+    if (B == 0) return VDB_OK;
+    const int D = ix->dim;
+    const bool host = mem == VDB_MEM_HOST;
+    if (host && !all_finite(queries, (int64_t)B * D)) return set_error(VDB_ERR_NONFINITE, "query contains NaN or Inf");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // as vdb_index_search_groups: the caller's stream, or for a host-memory call without one the
+    // stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const MmrScratch sc = mmr_scratch(B, D, k, fetch_k, N, host, masked, out_keys != nullptr, out_mmr != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    const float* Qd = queries;
+    const uint32_t* md = masked ? row_mask : nullptr;
+    float* out_s = out_scores;
+    int64_t* out_i = out_indices;
+    double* out_k = out_keys;
+    double* out_m = out_mmr;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+            if (masked) {
+                std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+                std::memset(h + (sc.mask - sc.in0) + sc.mask_words * 4, 0, 64 * 4);
+            }
+        });
+        if (rc) return rc;
+        Qd = reinterpret_cast<const float*>(dev + sc.q);
+        md = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        out_k = out_keys ? reinterpret_cast<double*>(dev + sc.out_k) : nullptr;
+        out_m = out_mmr ? reinterpret_cast<double*>(dev + sc.out_m) : nullptr;
+    }
+    if (N == 0) {  // an empty index: every slot "no result", as a search
+        HIP_TRY(launch_empty_results((int64_t)B * k, out_s, out_i, out_k, st));
+        // (out_mmr is -inf as the keys are: the same fill once more, with it in the keys' place)
+        if (out_m) HIP_TRY(launch_empty_results((int64_t)B * k, out_s, out_i, out_m, st));
+    } else {
+        float* fs = reinterpret_cast<float*>(dev + sc.fs);
+        int64_t* fi = reinterpret_cast<int64_t*>(dev + sc.fi);
+        double* fk = reinterpret_cast<double*>(dev + sc.fk);
+        // step 1: the candidate lists, the best fetch_k eligible rows with their keys, by the
+        // ordinary search in device memory on this stream (its own workspace, certificate and
+        // gated fallback; it counts the call in "searches" / "queries")
+        SearchOpts o;
+        rc = search_locked(ix, Qd, B, fetch_k, md, VDB_MEM_DEVICE, fs, fi, fk, 0, st, nullptr, o);
+        if (rc == kRetryBf16x3) {
+            o.force_b3 = true;
+            rc = search_locked(ix, Qd, B, fetch_k, md, VDB_MEM_DEVICE, fs, fi, fk, 0, st, nullptr, o);
+        }
+        if (rc) return rc;
+        // steps 2 and 3, block after block of queries over the same pair scratch
+        MmrArgs a{};
+        a.fi = fi; a.fk = fk; a.k_fetch = fetch_k; a.k = k; a.lambda = lambda;
+        a.X = ix->X; a.G = ix->G; a.D = D; a.nrm64 = ix->nrm64; a.count = N;
+        a.S = reinterpret_cast<double*>(dev + sc.S);
+        a.out_s = out_s; a.out_i = out_i; a.out_k = out_k; a.out_m = out_m; a.index_offset = index_offset;
+        const int qblock = mmr_query_block(fetch_k);
+        for (int b0 = 0; b0 < B; b0 += qblock) {
+            const int qb = std::min(qblock, B - b0);
+            HIP_TRY(launch_mmr_pairs(ix->metric, a, b0, qb, st));
+            HIP_TRY(launch_mmr_select(ix->metric, a, b0, qb, st));
+        }
+    }
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+        if (out_keys) std::memcpy(out_keys, r + (sc.out_k - sc.out0), (size_t)B * k * 8);
+        if (out_mmr) std::memcpy(out_mmr, r + (sc.out_m - sc.out0), (size_t)B * k * 8);
+    }
+    if (N == 0) {  // (a non-empty index's call was counted by its inner search)
+        ix->n_searches++;
+        ix->n_queries += B;
+    }
+    ix->n_mmr_searches++;
+    ix->n_mmr_queries += B;
     return VDB_OK;
 }
 

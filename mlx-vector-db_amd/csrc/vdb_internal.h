@@ -380,6 +380,20 @@ struct GroupExactArgs {
 size_t group_exact_lds_bytes(int k);
 hipError_t launch_group_exact(int metric, const GroupExactArgs& a, int n_queries, int n_seg, hipStream_t st);
 
+// MMR search (vdb_mmr.hip, vdb_index_search_mmr).  fi / fk [n_queries][k_fetch]: the candidate lists
+// (local rows, -1 = none, ranked by (key desc, row asc)) and their keys; S [qb][k_fetch][k_fetch]: the
+// pair similarities of one block of queries.  Both launches take the block's first query b0 and its
+// qb <= mmr_query_block(k_fetch) queries (vdb_mmr_plan.h): pairs fills S for the valid positions of
+// each list, select reads it and writes out_* [b][k] (out_k / out_m optional) in pick order.
+struct MmrArgs {
+    const int64_t* fi; const double* fk; int k_fetch; int k; double lambda;
+    const float* X; int G; int D; const double* nrm64; int64_t count;
+    double* S;
+    float* out_s; int64_t* out_i; double* out_k; double* out_m; int64_t index_offset;
+};
+hipError_t launch_mmr_pairs(int metric, const MmrArgs& a, int b0, int qb, hipStream_t st);
+hipError_t launch_mmr_select(int metric, const MmrArgs& a, int b0, int qb, hipStream_t st);
+
 // Merge sorted fp64-key lists.  Element (q, j, e) lives at q*sq + j*sj + e, lists
 // have Lk entries; output [nq][KP] sorted.
 hipError_t launch_merge_f64_u32(int KP, const double* lk, const uint32_t* li, int n_lists, int Lk,

@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
     "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
-    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -109,6 +109,8 @@ def load_library():
             "vdb_index_set_groups": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
             "vdb_index_search_groups": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
                                                 c_vp]),
+            "vdb_index_search_mmr": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_double, c_vp, c_i32, c_vp, c_vp,
+                                             c_vp, c_vp, c_i64, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -531,6 +533,51 @@ class NativeIndex:
             self._h, ctypes.c_void_p(q_ptr), int(n_queries), int(k), ctypes.c_void_p(mask_ptr or None), MEM_DEVICE,
             ctypes.c_void_p(out_scores_ptr), ctypes.c_void_p(out_idx_ptr), ctypes.c_void_p(out_groups_ptr or None),
             ctypes.c_void_p(out_keys_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
+
+    # -- MMR search --------------------------------------------------------------
+    def search_mmr(self, queries: np.ndarray, k: int, fetch_k: int, lam: float, row_mask: Optional[np.ndarray] = None,
+                   with_keys: bool = False, with_mmr: bool = False, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_mmr, host memory: of each query's best ``fetch_k`` rows the
+        ``k`` picked greedily by ``lam * relevance - (1 - lam) * (greatest similarity to a picked
+        row)``, in pick order.  Returns (scores f32 [B,k], indices i64 [B,k][, keys f64 [B,k]][, mmr
+        f64 [B,k]]); slots past min(k, candidates) are 0 / -1 / -inf / -inf."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must have shape (B, {self.dim}), got {np.shape(queries)}")
+        B = q.shape[0]
+        k = int(k)
+        scores = np.empty((B, max(k, 0)), dtype=np.float32)  # (a bad k is the library's to refuse)
+        idx = np.empty((B, max(k, 0)), dtype=np.int64)
+        keys = np.empty((B, max(k, 0)), dtype=np.float64) if with_keys else None
+        mmr = np.empty((B, max(k, 0)), dtype=np.float64) if with_mmr else None
+        mask_p = None
+        if row_mask is not None:
+            m = np.ascontiguousarray(row_mask, dtype=np.uint32)
+            need = (self.count() + 31) // 32
+            if m.size < need:
+                raise ValueError(f"row_mask needs {need} uint32 words, got {m.size}")
+            mask_p = _ptr(m)
+        _check(self._lib.vdb_index_search_mmr(self._h, _ptr(q), B, k, int(fetch_k), float(lam), mask_p, MEM_HOST,
+                                              _ptr(scores), _ptr(idx), _ptr(keys) if keys is not None else None,
+                                              _ptr(mmr) if mmr is not None else None, int(index_offset), None))
+        out = (scores, idx)
+        if with_keys:
+            out += (keys,)
+        if with_mmr:
+            out += (mmr,)
+        return out
+
+    def search_mmr_device(self, q_ptr: int, n_queries: int, k: int, fetch_k: int, lam: float, out_scores_ptr: int,
+                          out_idx_ptr: int, out_keys_ptr: int = 0, out_mmr_ptr: int = 0, mask_ptr: int = 0,
+                          index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_mmr with device-memory arguments; stream-ordered, nothing is read back."""
+        _check(self._lib.vdb_index_search_mmr(
+            self._h, ctypes.c_void_p(q_ptr), int(n_queries), int(k), int(fetch_k), float(lam),
+            ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, ctypes.c_void_p(out_scores_ptr), ctypes.c_void_p(out_idx_ptr),
+            ctypes.c_void_p(out_keys_ptr or None), ctypes.c_void_p(out_mmr_ptr or None), int(index_offset),
+            ctypes.c_void_p(stream or None)))
 
 
 class NativeShards:

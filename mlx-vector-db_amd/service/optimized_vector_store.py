@@ -48,6 +48,10 @@ _NO_OPERATOR_MSG = "Keine kompilierte Ähnlichkeitsfunktion verfügbar."
 # per group; POST /vectors/query_groups bounds its body by the same two
 GROUP_MAX_K = 128
 GROUP_MAX_SIZE = 100
+# mmr_query: the most rows per query and the most candidates they are picked from (include/vdb.h
+# vdb_index_search_mmr); POST /vectors/mmr_query answers a value outside them with 400
+MMR_MAX_K = 200
+MMR_MAX_FETCH = 200
 
 
 # half the smallest measured crossover of the row-list search against the masked
@@ -905,6 +909,65 @@ class MLXVectorStore:
                 valid = i2[j] >= 0
                 out[b].append({"group": values[g],
                                "hits": hits_of(i2[j][valid].tolist(), s2[j][valid].astype(np.float64).tolist())})
+            return out
+
+    # ---- MMR query ---------------------------------------------------------------------
+    def mmr_query(self, query_vector: Union[np.ndarray, Any], k: int = 10, fetch_k: Optional[int] = None,
+                  lambda_mult: float = 0.5, filter_metadata: Optional[Dict] = None) -> Tuple:
+        """``k`` rows that are relevant to the query and unlike each other (maximal marginal
+        relevance) -> (indices, scores, metadata) as ``query`` returns them, in pick order.  Of the
+        best ``fetch_k`` rows (``None``: min(200, max(4 k, 20))) each pick maximises ``lambda_mult *
+        relevance - (1 - lambda_mult) * (greatest similarity to a row picked before)``; both terms
+        are the exact ranking keys (cosine similarity; minus the SQUARED distance for euclidean), so
+        ``lambda_mult`` = 1 is ``query`` and 0 looks at diversity alone.  Exact and the same for
+        every precision (include/vdb.h vdb_index_search_mmr).  The reference has no such read: its
+        RAG context fills with overlapping chunks of one paragraph
+        (integrations/mlx_lm_pipeline.py:646-756)."""
+        q = _as_matrix(query_vector)
+        if q.ndim == 2 and q.shape[0] == 1:
+            q = q[0]
+        if q.ndim != 1:
+            raise ValueError(f"mmr_query takes one vector of shape (dim,) or (1, dim), got {q.shape}; "
+                             "use batch_mmr_query for several")
+        return self._mmr_search(q[None, :], k, fetch_k, lambda_mult, filter_metadata)[0]
+
+    def batch_mmr_query(self, query_vectors: Union[np.ndarray, Any], k: int = 10, fetch_k: Optional[int] = None,
+                        lambda_mult: float = 0.5, filter_metadata: Optional[Dict] = None) -> List[Tuple]:
+        """``mmr_query`` for a [B, dim] block of queries from one device call: one (indices, scores,
+        metadata) tuple per query."""
+        q = _as_matrix(query_vectors)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError(f"query_vectors must be 2-D (B, dim), got {q.shape}")
+        return self._mmr_search(q, k, fetch_k, lambda_mult, filter_metadata)
+
+    def _mmr_search(self, Q: np.ndarray, k, fetch_k, lambda_mult, filter_metadata: Optional[Dict]):
+        if len(self._devices()) > 1:
+            raise NotImplementedError("MMR query is not supported on a multi-device store")
+        k = int(k)
+        if not 1 <= k <= MMR_MAX_K:
+            raise ValueError(f"k must be in [1, {MMR_MAX_K}], got {k}")
+        fetch_k = min(MMR_MAX_FETCH, max(4 * k, 20)) if fetch_k is None else int(fetch_k)
+        if not k <= fetch_k <= MMR_MAX_FETCH:
+            raise ValueError(f"fetch_k must be in [k, {MMR_MAX_FETCH}], got fetch_k={fetch_k} k={k}")
+        lam = float(lambda_mult)
+        if not 0.0 <= lam <= 1.0:  # (a NaN fails both comparisons)
+            raise ValueError(f"lambda_mult must be in [0, 1], got {lambda_mult}")
+        B = Q.shape[0]
+        with _Read(self._rw):
+            # (never the graph path, never the coalescer: one exact device call for the block)
+            mask = self._range_mask(Q, filter_metadata)  # None: no filter; False: nothing to search
+            if mask is False or B == 0:
+                return [([], [], []) for _ in range(B)]
+            scores, idx = self._index.search_mmr(Q, k, fetch_k, lam, row_mask=mask)
+            meta = self._metadata
+            out = []
+            for b in range(B):
+                valid = idx[b] >= 0
+                ib = idx[b][valid].tolist()
+                out.append((ib, scores[b][valid].astype(np.float64).tolist(),
+                            [meta[i] if i < len(meta) else {} for i in ib]))
             return out
 
     # ---- misc API ----------------------------------------------------------------------
