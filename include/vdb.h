@@ -152,7 +152,8 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * are "range_searches", "range_queries"), "group_fetch" (rows vdb_index_search_groups' inner
  * search fetches, 0 = auto, 1..200) and "group_force_exact" (0/1; its stats "group_rows",
  * "group_sets", "group_searches", "group_queries", "group_fallback_queries" are described
- * there).  Stats also: "searches", "queries",
+ * there; vdb_index_search_mmr's are "mmr_searches", "mmr_queries"; vdb_index_search_recommend's
+ * "recommend_searches", "recommend_queries", "recommend_bad_queries").  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -428,6 +429,70 @@ int32_t vdb_index_search_mmr(vdb_index* idx, const float* queries, int32_t n_que
                              const uint32_t* row_mask, int32_t mem,
                              float* out_scores, int64_t* out_indices, double* out_keys,
                              double* out_mmr, int64_t index_offset, void* stream);
+
+/* --- recommend search: rows like stored examples ------------------------------------
+ * Replaces: nothing the reference has.  Every other read takes a query VECTOR; "more like this
+ * stored row", "more like these chunks and not like those" and "more like this document" take
+ * stored rows (Qdrant's recommend with positive and negative ids, Pinecone's query by id, Weaviate's
+ * nearObject).  Without this call a user copies each example to the host, averages in numpy in
+ * whatever order it picks, searches for k + examples rows and drops the examples; the averaged
+ * query has near-ties, so a last-bit difference changes the list, and a device-memory caller cannot
+ * do it at all.
+ *
+ *   pos_offsets [n_queries + 1], pos_rows [n_pos]: query b's positive examples are
+ *                pos_rows[pos_offsets[b] .. pos_offsets[b + 1]), stored row ids in [0, count) in any
+ *                order (the CSR form of vdb_index_search_rows' lists).  A row may repeat and counts
+ *                as often as it appears; it may stand in both lists.
+ *   neg_offsets, neg_rows, n_neg: the negatives in the same form; neg_offsets == NULL with n_neg
+ *                == 0: no query has negatives.
+ *   n_pos, n_neg host scalars, the lengths of the id arrays: the launches are sized from them, so a
+ *                device-memory call reads nothing back.
+ *   A query has at most 64 examples, positives and negatives together; k is in 1..136 (200 - 64:
+ *   the inner fetch of k + examples rows never leaves the certified fast path's 200).
+ *   out_scores / out_indices / out_keys: [n_queries, k], written as a search writes them; out_keys
+ *                may be NULL.
+ *   out_queries  NULL, or [n_queries, dim] fp32: the query vectors that were built.
+ *   row_mask, mem, index_offset, stream: as vdb_index_search; all pointers of one memory kind.
+ *                n_queries == 0 is VDB_OK.
+ * The built query, element d of query b, every operation a separate fp64 operation: acc = 0.0; for
+ * the positives in list order acc = acc + e, with e = (double)x[d] for euclidean and e =
+ * (double)x[d] / max(norm, 1e-8) for cosine (one fp64 divide per element by the row's canonical
+ * norm, the clamp a key uses); mp = acc / (double)(number of positives); mn likewise over the
+ * negatives; t = mp without negatives, else (mp + mp) - mn (Qdrant's average-vector rule); q[d] =
+ * (float)t, round to nearest even.  Elements are independent: nothing depends on how they are dealt
+ * to threads.
+ * The result is what vdb_index_search ranks for q_b under row_mask (canonical fp64 key desc, then
+ * row asc) with every row of the query's positives or negatives left out: the first k of what
+ * remains, scores rounded as a search rounds them; slots past the eligible non-example rows hold
+ * index -1 / score 0 / key -inf.  Examples need not be eligible under row_mask.  The result is the
+ * same bytes for every precision setting and both memory kinds.  For euclidean, one positive p and
+ * no negatives give, byte for byte, the first k slots of a search with row p as the query and k + 1
+ * results with row p struck out, since (float)((double)x / 1.0) == x.  Cosine has no such identity:
+ * its query is the normalised row rounded to fp32, not the row.
+ * Queries answered with every slot "no result" (out_queries holds zeros for them): (1) a query
+ * without a positive example, which is no error in either memory kind; (2) a query whose built
+ * vector has a non-finite element (euclidean rows above about 1.1e38 only); (3) on a device-memory
+ * call, which is not validated: a query with an id outside [0, count) or more than 64 examples
+ * (offsets are clamped to [0, n_pos] / [0, n_neg] and nothing out of bounds is read).  (2) and (3)
+ * are counted on the device in stat "recommend_bad_queries".
+ * How: one kernel builds the queries (one workgroup per query, a thread per 256th element, the
+ * examples walked in order), the inner search fetches k' = k + E rows (host memory: E = the largest
+ * example count of the call; device memory: min(64, n_pos + n_neg)), one kernel drops the examples
+ * in order (one wave per query).
+ * Errors, host-memory calls, before anything is launched: k outside [1, 136], n_queries < 0, a NULL
+ * pos_offsets / out_scores / out_indices with n_queries > 0, neg_offsets NULL with n_neg != 0,
+ * offsets that decrease or pass their n_pos / n_neg, an id outside [0, count), a query with more
+ * than 64 examples, a bad mem -> VDB_ERR_INVALID (no stat moves).  There are no caller vectors, so
+ * no VDB_ERR_NONFINITE.  An empty index with empty lists gives every slot "no result".  Takes the
+ * index's shared lock and a per-search workspace, as vdb_index_search_mmr does.  Stats (cumulative,
+ * successful calls): "recommend_searches", "recommend_queries", "recommend_bad_queries";
+ * "searches" / "queries" move once per call through the inner search. */
+int32_t vdb_index_search_recommend(vdb_index* idx, int32_t n_queries, int32_t k,
+                                   const int64_t* pos_offsets, const int64_t* pos_rows, int64_t n_pos,
+                                   const int64_t* neg_offsets, const int64_t* neg_rows, int64_t n_neg,
+                                   const uint32_t* row_mask, int32_t mem,
+                                   float* out_scores, int64_t* out_indices, double* out_keys, float* out_queries,
+                                   int64_t index_offset, void* stream);
 
 /* --- multi-GPU merge -----------------------------------------------------------
  * Merge per-shard top-k lists (all device memory, already all-gathered):

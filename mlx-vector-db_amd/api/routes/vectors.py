@@ -79,6 +79,20 @@ class VectorMMRQuery(VectorQuery):
     lambda_mult: float = Field(default=0.5, description="1 = relevance only, 0 = diversity only")
 
 
+class VectorRecommendQuery(BaseModel):
+    """Rows like the stored examples ``positive`` and unlike ``negative``: row indices, or with
+    ``key`` (a metadata field, e.g. "doc_id") values of that field, every row holding one of them an
+    example.  The store checks the limits (k at most 136, at most 64 examples after resolution, an
+    index inside the store, a value some row holds); anything outside them is a 400."""
+    user_id: str
+    model_id: str
+    positive: List[Union[int, str]] = Field(..., description="Examples to be like: row indices, or values of `key`")
+    negative: List[Union[int, str]] = Field(default_factory=list, description="Examples to be unlike")
+    k: int = Field(default=10, description="Rows returned")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    key: Optional[str] = Field(default=None, description="Metadata field the examples are values of")
+
+
 class VectorRangeQuery(BaseModel):
     """Every stored row within ``threshold`` of the query: a minimum similarity for a cosine
     store, a maximum distance for a euclidean one."""
@@ -420,6 +434,32 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in MMR query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"MMR query failed: {e}")
+
+    @router.post("/recommend", response_model=VectorQueryResponse)
+    async def recommend_vectors(request: VectorRecommendQuery, api_key: str = Depends(auth)):
+        """The ``k`` rows most like the stored examples ``positive`` and unlike ``negative``, the
+        examples left out, in /vectors/query's format.  A bad request (k or the example count
+        outside their limits, an index outside the store, a ``key`` value no row holds: the store's
+        ValueError) is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            loop = asyncio.get_running_loop()
+            indices, scores, metas = await loop.run_in_executor(
+                mgr._executor, lambda: store.recommend(request.positive, request.negative, k=request.k,
+                                                       filter_metadata=request.filter_metadata, key=request.key))
+            return VectorQueryResponse(results=format_query_results(store.config.metric, indices, scores, metas),
+                                       query_time_ms=(time.time() - t0) * 1000,
+                                       total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Recommend failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Recommend failed: {e}")
+        except Exception as e:
+            logger.error("Error in recommend: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Recommend failed: {e}")
 
     @router.post("/batch_query", response_model=BatchQueryResponse)
     async def batch_query_vectors(request: BatchQueryRequest, api_key: str = Depends(auth)):

@@ -28,6 +28,7 @@
 #include "vdb_range_plan.h"
 #include "vdb_group_plan.h"
 #include "vdb_mmr_plan.h"
+#include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
 #include "vdb_internal.h"
 
@@ -59,6 +60,7 @@ constexpr int64_t kRowAlign = ROW_ALIGN;   // capacity granule, a multiple of ev
 
 constexpr size_t kGatedExactBytes = 256u << 20;  // device-gated fallback lists sized for every query of a batch
 constexpr int kSubsetBadWord = 12;        // d_xmax word (8 bytes each) counting a row-list search's skipped ids
+constexpr int kRecommendBadWord = 13;     // d_xmax word counting the queries a recommend search flagged on the device
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 inline int next_pow2(int v) {
@@ -251,6 +253,9 @@ struct vdb_index {
     int64_t group_force_exact = 0;  // knob: every query takes the exact fallback (tests, A/B)
     // vdb_index_search_mmr: calls and queries (successful calls)
     std::atomic<int64_t> n_mmr_searches{0}, n_mmr_queries{0};
+    // vdb_index_search_recommend: calls and queries (successful calls); the queries its build kernel
+    // flagged are counted on the device (d_xmax + kRecommendBadWord)
+    std::atomic<int64_t> n_rec_searches{0}, n_rec_queries{0};
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -858,7 +863,8 @@ int32_t vdb_index_create(int32_t dim, int32_t metric, int32_t device, vdb_index*
     hipError_t e = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
     // d_xmax: [0, 32) the residual maxima, [32, 36) the non-finite count, [64, 96) and
     // [128, 192) an add's snapshot of the maxima and of d_i8 (restored when the add is rejected),
-    // [96, 104) the ids row-list searches skipped (kSubsetBadWord; cumulative, a clear keeps it)
+    // [96, 104) the ids row-list searches skipped (kSubsetBadWord; cumulative, a clear keeps it),
+    // [104, 112) the queries recommend searches flagged (kRecommendBadWord; likewise)
     if (e == hipSuccess) e = hipMalloc(&ix->d_xmax, 192);
     if (e == hipSuccess) e = zero_now(ix->d_xmax, 192, ix->stream);
     if (e == hipSuccess) e = hipMalloc(&ix->d_i8, 64);
@@ -1158,6 +1164,16 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "group_queries") *value = ix->n_group_queries.load();
     else if (n == "mmr_searches") *value = ix->n_mmr_searches.load();
     else if (n == "mmr_queries") *value = ix->n_mmr_queries.load();
+    else if (n == "recommend_searches") *value = ix->n_rec_searches.load();
+    else if (n == "recommend_queries") *value = ix->n_rec_queries.load();
+    else if (n == "recommend_bad_queries") {  // counted by the build kernel: after the searches queued so far
+        HIP_TRY(hipSetDevice(ix->device));
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpy(&bad, ix->d_xmax + kRecommendBadWord, sizeof(bad), hipMemcpyDeviceToHost));
+        *value = (int64_t)bad;
+    }
     else if (n == "group_fallback_queries") {  // counted by the select kernel: after the searches queued so far
         unsigned long long fb = 0;
         if (ix->d_group_fb) {
@@ -2812,6 +2828,141 @@ int32_t vdb_index_search_mmr(vdb_index* ix, const float* queries, int32_t B, int
     }
     ix->n_mmr_searches++;
     ix->n_mmr_queries += B;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_recommend(vdb_index* ix, int32_t B, int32_t k, const int64_t* pos_offsets,
+                                   const int64_t* pos_rows, int64_t n_pos, const int64_t* neg_offsets,
+                                   const int64_t* neg_rows, int64_t n_neg, const uint32_t* row_mask, int32_t mem,
+                                   float* out_scores, int64_t* out_indices, double* out_keys, float* out_queries,
+                                   int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    // everything checked before any launch (a host-memory call's lists under the lock, below)
+    switch (rec_validate(B, k, n_pos, n_neg, pos_offsets != nullptr, pos_rows != nullptr, neg_offsets != nullptr,
+                         neg_rows != nullptr, out_scores != nullptr, out_indices != nullptr, mem)) {
+        case kRecBadQueries: return set_error(VDB_ERR_INVALID, "n_queries must be >= 0, got %d", B);
+        case kRecBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", kRecMaxK, k);
+        case kRecBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+        case kRecBadCounts:
+            return set_error(VDB_ERR_INVALID, "n_pos and n_neg must be >= 0, and n_neg 0 without neg_offsets (got %lld, %lld)",
+                             (long long)n_pos, (long long)n_neg);
+        case kRecNullPointer: return set_error(VDB_ERR_INVALID, "NULL list/output pointer");
+        default: break;
+    }
+    if (B == 0) return VDB_OK;
+    const int D = ix->dim;
+    const bool host = mem == VDB_MEM_HOST;
+    const bool has_neg = neg_offsets != nullptr;
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    int examples = rec_fetch_examples_device(n_pos, n_neg);
+    if (host) {
+        int64_t at = 0;
+        int which = 0;
+        const int vr = rec_validate_lists(pos_offsets, pos_rows, n_pos, neg_offsets, neg_rows, n_neg, B, N, &at, &which,
+                                          &examples);
+        const char* name = which ? "neg" : "pos";
+        const int64_t* offs = which ? neg_offsets : pos_offsets;
+        const int64_t* rows = which ? neg_rows : pos_rows;
+        switch (vr) {
+            case kRecOk: break;
+            case kRecBadOffsets:
+                return set_error(VDB_ERR_INVALID, "%s_offsets[%lld] = %lld: offsets must ascend from >= 0 to <= n_%s (%lld)",
+                                 name, (long long)at, (long long)offs[at], name, (long long)(which ? n_neg : n_pos));
+            case kRecBadId:
+                return set_error(VDB_ERR_INVALID, "%s_rows[%lld] = %lld is outside [0, %lld)", name, (long long)at,
+                                 (long long)rows[at], (long long)N);
+            default:
+                return set_error(VDB_ERR_INVALID, "query %lld has more than %d examples", (long long)at, kRecMaxExamples);
+        }
+    }
+    // as vdb_index_search_mmr: the caller's stream, or for a host-memory call without one the
+    // stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const int fetch_k = rec_fetch_k(k, examples);
+    const RecScratch sc = rec_scratch(B, D, k, fetch_k, N, n_pos, n_neg, host, has_neg, masked, out_keys != nullptr,
+                                      out_queries != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    RecommendArgs a{};
+    a.pos_offs = pos_offsets; a.pos_rows = pos_rows; a.n_pos = n_pos;
+    a.neg_offs = neg_offsets; a.neg_rows = neg_rows; a.n_neg = n_neg;
+    const uint32_t* md = masked ? row_mask : nullptr;
+    a.out_s = out_scores; a.out_i = out_indices; a.out_k = out_keys;
+    if (host) {  // the lists and the mask go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.pos_offs - sc.in0), pos_offsets, ((size_t)B + 1) * 8);
+            if (n_pos > 0) std::memcpy(h + (sc.pos_rows - sc.in0), pos_rows, (size_t)n_pos * 8);
+            if (has_neg) {
+                std::memcpy(h + (sc.neg_offs - sc.in0), neg_offsets, ((size_t)B + 1) * 8);
+                if (n_neg > 0) std::memcpy(h + (sc.neg_rows - sc.in0), neg_rows, (size_t)n_neg * 8);
+            }
+            if (masked) {
+                std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+                std::memset(h + (sc.mask - sc.in0) + sc.mask_words * 4, 0, 64 * 4);
+            }
+        });
+        if (rc) return rc;
+        a.pos_offs = reinterpret_cast<const int64_t*>(dev + sc.pos_offs);
+        a.pos_rows = reinterpret_cast<const int64_t*>(dev + sc.pos_rows);
+        a.neg_offs = has_neg ? reinterpret_cast<const int64_t*>(dev + sc.neg_offs) : nullptr;
+        a.neg_rows = has_neg ? reinterpret_cast<const int64_t*>(dev + sc.neg_rows) : nullptr;
+        md = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_k = out_keys ? reinterpret_cast<double*>(dev + sc.out_k) : nullptr;
+    }
+    a.X = ix->X; a.G = ix->G; a.D = D; a.nrm64 = ix->nrm64; a.count = N;
+    a.Q = reinterpret_cast<float*>(dev + sc.q);
+    a.flag = reinterpret_cast<int*>(dev + sc.flag);
+    a.bad = ix->d_xmax + kRecommendBadWord;
+    a.k = k; a.k_fetch = fetch_k; a.index_offset = index_offset;
+    // step 1: the built queries and their flags (an empty index: every query is flagged or empty)
+    HIP_TRY(launch_recommend_build(ix->metric, a, B, st));
+    if (N == 0) {  // every slot "no result", as a search
+        HIP_TRY(launch_empty_results((int64_t)B * k, a.out_s, a.out_i, a.out_k, st));
+    } else {
+        float* fs = reinterpret_cast<float*>(dev + sc.fs);
+        int64_t* fi = reinterpret_cast<int64_t*>(dev + sc.fi);
+        double* fk = reinterpret_cast<double*>(dev + sc.fk);
+        // step 2: the best fetch_k eligible rows of every built query with their keys, by the
+        // ordinary search in device memory on this stream (its own workspace, certificate and
+        // gated fallback; it counts the call in "searches" / "queries")
+        SearchOpts o;
+        rc = search_locked(ix, a.Q, B, fetch_k, md, VDB_MEM_DEVICE, fs, fi, fk, 0, st, nullptr, o);
+        if (rc == kRetryBf16x3) {
+            o.force_b3 = true;
+            rc = search_locked(ix, a.Q, B, fetch_k, md, VDB_MEM_DEVICE, fs, fi, fk, 0, st, nullptr, o);
+        }
+        if (rc) return rc;
+        // step 3: the examples dropped, the first k kept
+        a.fi = fi; a.fk = fk;
+        HIP_TRY(launch_recommend_select(ix->metric, a, B, st));
+    }
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+        if (out_keys) std::memcpy(out_keys, r + (sc.out_k - sc.out0), (size_t)B * k * 8);
+        if (out_queries) std::memcpy(out_queries, r + (sc.q - sc.out0), (size_t)B * D * 4);
+    } else if (out_queries) {
+        HIP_TRY(hipMemcpyAsync(out_queries, a.Q, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
+    }
+    if (N == 0) {  // (a non-empty index's call was counted by its inner search)
+        ix->n_searches++;
+        ix->n_queries += B;
+    }
+    ix->n_rec_searches++;
+    ix->n_rec_queries += B;
     return VDB_OK;
 }
 

@@ -394,6 +394,24 @@ struct MmrArgs {
 hipError_t launch_mmr_pairs(int metric, const MmrArgs& a, int b0, int qb, hipStream_t st);
 hipError_t launch_mmr_select(int metric, const MmrArgs& a, int b0, int qb, hipStream_t st);
 
+// Recommend search (vdb_recommend.hip, vdb_index_search_recommend).  pos_offs / pos_rows (n_pos ids)
+// and neg_offs / neg_rows (n_neg ids; neg_offs == nullptr: no negatives): the queries' example lists
+// in CSR form, device memory, read under the clamp of vdb_recommend_plan.h whatever they hold.  Build
+// writes the queries Q [n_queries][D] and flag [n_queries] (0, or the reason the query is "no
+// result"; *bad += the queries flagged for a bad list or a non-finite element); count == 0 is
+// allowed there (no row is read).  Select reads the fetched lists fi / fk [n_queries][k_fetch] (local
+// rows, -1 = none, ranked by (key desc, row asc)) and writes out_* [n_queries][k] (out_k optional).
+struct RecommendArgs {
+    const int64_t* pos_offs; const int64_t* pos_rows; int64_t n_pos;
+    const int64_t* neg_offs; const int64_t* neg_rows; int64_t n_neg;
+    const float* X; int G; int D; const double* nrm64; int64_t count;
+    float* Q; int* flag; unsigned long long* bad;
+    const int64_t* fi; const double* fk; int k_fetch; int k;
+    float* out_s; int64_t* out_i; double* out_k; int64_t index_offset;
+};
+hipError_t launch_recommend_build(int metric, const RecommendArgs& a, int n_queries, hipStream_t st);
+hipError_t launch_recommend_select(int metric, const RecommendArgs& a, int n_queries, hipStream_t st);
+
 // Merge sorted fp64-key lists.  Element (q, j, e) lives at q*sq + j*sj + e, lists
 // have Lk entries; output [nq][KP] sorted.
 hipError_t launch_merge_f64_u32(int KP, const double* lk, const uint32_t* li, int n_lists, int Lk,

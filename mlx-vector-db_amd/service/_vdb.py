@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
     "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
-    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -111,6 +111,8 @@ def load_library():
                                                 c_vp]),
             "vdb_index_search_mmr": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_double, c_vp, c_i32, c_vp, c_vp,
                                              c_vp, c_vp, c_i64, c_vp]),
+            "vdb_index_search_recommend": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32,
+                                                   c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -577,6 +579,62 @@ class NativeIndex:
             self._h, ctypes.c_void_p(q_ptr), int(n_queries), int(k), int(fetch_k), float(lam),
             ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, ctypes.c_void_p(out_scores_ptr), ctypes.c_void_p(out_idx_ptr),
             ctypes.c_void_p(out_keys_ptr or None), ctypes.c_void_p(out_mmr_ptr or None), int(index_offset),
+            ctypes.c_void_p(stream or None)))
+
+    # -- recommend search ----------------------------------------------------------
+    def search_recommend(self, positive, negative=None, k: int = 10, row_mask: Optional[np.ndarray] = None,
+                         with_keys: bool = False, with_queries: bool = False, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_recommend, host memory: query b is built on the device
+        from the stored rows ``positive[b]`` (and ``negative[b]``: their means, ``2 mp - mn``) and
+        answered as ``search`` would answer that vector, the examples left out.  ``positive`` /
+        ``negative``: a sequence of integer row-id sequences, one per query (``negative=None``: no
+        query has negatives), packed to CSR here.  Returns (scores f32 [B,k], indices i64 [B,k][,
+        keys f64 [B,k]][, queries f32 [B,dim]]); a query without a positive is all 0 / -1 / -inf.  A
+        malformed list, more than 64 examples or ``k`` outside [1, 136] raises ValueError."""
+        po, pr = pack_row_lists(positive)
+        B = po.size - 1
+        no = nr = None
+        if negative is not None:
+            no, nr = pack_row_lists(negative)
+            if no.size - 1 != B:
+                raise ValueError(f"negative needs one list per query ({B}), got {no.size - 1}")
+        k = int(k)
+        scores = np.empty((B, max(k, 0)), dtype=np.float32)  # (a bad k is the library's to refuse)
+        idx = np.empty((B, max(k, 0)), dtype=np.int64)
+        keys = np.empty((B, max(k, 0)), dtype=np.float64) if with_keys else None
+        qs = np.empty((B, self.dim), dtype=np.float32) if with_queries else None
+        mask_p = None
+        if row_mask is not None:
+            m = np.ascontiguousarray(row_mask, dtype=np.uint32)
+            need = (self.count() + 31) // 32
+            if m.size < need:
+                raise ValueError(f"row_mask needs {need} uint32 words, got {m.size}")
+            mask_p = _ptr(m)
+        _check(self._lib.vdb_index_search_recommend(
+            self._h, B, k, _ptr(po), _ptr(pr) if pr.size else None, pr.size,
+            _ptr(no) if no is not None else None, _ptr(nr) if nr is not None and nr.size else None,
+            nr.size if nr is not None else 0, mask_p, MEM_HOST, _ptr(scores), _ptr(idx),
+            _ptr(keys) if keys is not None else None, _ptr(qs) if qs is not None else None, int(index_offset), None))
+        out = (scores, idx)
+        if with_keys:
+            out += (keys,)
+        if with_queries:
+            out += (qs,)
+        return out
+
+    def search_recommend_device(self, n_queries: int, k: int, pos_offsets_ptr: int, pos_rows_ptr: int, n_pos: int,
+                                out_scores_ptr: int, out_idx_ptr: int, neg_offsets_ptr: int = 0, neg_rows_ptr: int = 0,
+                                n_neg: int = 0, out_keys_ptr: int = 0, out_queries_ptr: int = 0, mask_ptr: int = 0,
+                                index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_recommend with device-memory arguments (int64 offsets and rows);
+        stream-ordered, nothing is validated on the host and nothing is read back (a query with a bad
+        list comes back empty and counts in stat ``recommend_bad_queries``)."""
+        _check(self._lib.vdb_index_search_recommend(
+            self._h, int(n_queries), int(k), ctypes.c_void_p(pos_offsets_ptr or None),
+            ctypes.c_void_p(pos_rows_ptr or None), int(n_pos), ctypes.c_void_p(neg_offsets_ptr or None),
+            ctypes.c_void_p(neg_rows_ptr or None), int(n_neg), ctypes.c_void_p(mask_ptr or None), MEM_DEVICE,
+            ctypes.c_void_p(out_scores_ptr or None), ctypes.c_void_p(out_idx_ptr or None),
+            ctypes.c_void_p(out_keys_ptr or None), ctypes.c_void_p(out_queries_ptr or None), int(index_offset),
             ctypes.c_void_p(stream or None)))
 
 

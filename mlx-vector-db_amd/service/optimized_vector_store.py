@@ -52,6 +52,11 @@ GROUP_MAX_SIZE = 100
 # vdb_index_search_mmr); POST /vectors/mmr_query answers a value outside them with 400
 MMR_MAX_K = 200
 MMR_MAX_FETCH = 200
+# recommend: the most rows per query and the most examples (positives and negatives together) a
+# query is built from (include/vdb.h vdb_index_search_recommend); POST /vectors/recommend answers a
+# value outside them with 400
+REC_MAX_K = 136
+REC_MAX_EXAMPLES = 64
 
 
 # half the smallest measured crossover of the row-list search against the masked
@@ -969,6 +974,82 @@ class MLXVectorStore:
                 out.append((ib, scores[b][valid].astype(np.float64).tolist(),
                             [meta[i] if i < len(meta) else {} for i in ib]))
             return out
+
+    # ---- recommend --------------------------------------------------------------------
+    def recommend(self, positive, negative=None, k: int = 10, filter_metadata: Optional[Dict] = None,
+                  key: Optional[Any] = None) -> Tuple:
+        """The ``k`` rows most like the stored examples ``positive`` and unlike ``negative`` ->
+        (indices, scores, metadata) as ``query`` returns them, best first, the examples themselves
+        left out.  With ``key=None`` the entries are row indices; with a metadata field (``key=
+        "doc_id"``) each entry is a value and every row that holds it becomes an example ("more
+        like this document" = all its chunks).  The query is built on the device, the mean of the
+        positives, or ``2 * mean(positive) - mean(negative)`` (for cosine over the normalised
+        rows), in one fixed fp64 order, so the answer is exact and the same for every precision
+        (include/vdb.h vdb_index_search_recommend).  At most 64 examples and ``k`` <= 136.  The
+        reference has no such read."""
+        return self.batch_recommend([(positive, negative)], k, filter_metadata, key)[0]
+
+    def batch_recommend(self, requests, k: int = 10, filter_metadata: Optional[Dict] = None,
+                        key: Optional[Any] = None) -> List[Tuple]:
+        """``recommend`` for a list of ``(positive, negative)`` pairs from one device call: one
+        (indices, scores, metadata) tuple per pair."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("recommend is not supported on a multi-device store")
+        k = int(k)
+        if not 1 <= k <= REC_MAX_K:
+            raise ValueError(f"k must be in [1, {REC_MAX_K}], got {k}")
+        requests = [(r[0], r[1] if len(r) > 1 else None) for r in requests]
+        B = len(requests)
+        with _Read(self._rw):
+            # (never the graph path, never the coalescer: one exact device call for the block)
+            n = self._vector_count
+            pos = [self._example_rows(p, key, n) for p, _ in requests]
+            neg = [self._example_rows(g, key, n) for _, g in requests]
+            for p, g in zip(pos, neg):
+                if p.size + g.size > REC_MAX_EXAMPLES:
+                    raise ValueError(f"a recommend query takes at most {REC_MAX_EXAMPLES} examples, positives and "
+                                     f"negatives together; got {p.size + g.size}")
+            empty = [([], [], []) for _ in range(B)]
+            if n == 0 or not any(p.size for p in pos):
+                return empty
+            if not self._compiled_similarity_fn:
+                raise RuntimeError(_NO_OPERATOR_MSG)
+            mask = None
+            if filter_metadata:
+                mask, eligible = self._meta_index.bitmap(filter_metadata, n)
+                if not eligible:
+                    return empty
+            scores, idx = self._index.search_recommend(pos, neg if any(g.size for g in neg) else None, k, row_mask=mask)
+            meta = self._metadata
+            out = []
+            for b in range(B):
+                valid = idx[b] >= 0
+                ib = idx[b][valid].tolist()
+                out.append((ib, scores[b][valid].astype(np.float64).tolist(),
+                            [meta[i] if i < len(meta) else {} for i in ib]))
+            return out
+
+    def _example_rows(self, entries, key, n: int) -> np.ndarray:
+        """The row ids of one example list (read lock held): the entries themselves (``key`` None:
+        integers in [0, n)), or every row whose metadata holds ``key`` with an entry's value."""
+        if entries is None:
+            return np.zeros(0, np.int64)
+        entries = list(entries)
+        if key is None:
+            for e in entries:
+                if isinstance(e, (bool, np.bool_)) or not isinstance(e, (int, np.integer)):
+                    raise ValueError(f"an example must be an integer row index (or pass key=), got {e!r}")
+                if not 0 <= int(e) < n:
+                    raise ValueError(f"row index {int(e)} is outside [0, {n})")
+            return np.asarray([int(e) for e in entries], np.int64).reshape(-1)
+        rows = []
+        for v in entries:
+            r = self._meta_index.rows_with(key, v)
+            r = r[r < n]
+            if r.size == 0:
+                raise ValueError(f"no row has {key!r} = {v!r}")
+            rows.append(r)
+        return np.concatenate(rows).astype(np.int64) if rows else np.zeros(0, np.int64)
 
     # ---- misc API ----------------------------------------------------------------------
     def _warmup_kernels(self):
