@@ -19,13 +19,14 @@ constexpr int RERANK_WAVES = 16;
 // Same keys (same canonical order) with the query pieces in registers and every
 // row piece of NB rows requested before the first FMA: one dependent round trip
 // per batch instead of np of them (D <= 256 MP).
-template <int METRIC, int NB, int MP>
-__device__ __forceinline__ void exact_keys_regs(const float (&qv)[MP][4], double qn, const float* __restrict__ X,
-                                                int G, int np, const uint32_t* rows, const double* xn, int nb,
-                                                double* out) {
+// In three steps, so that the finish requests a batch's pieces (exact_rows_load) before the batch
+// ahead of it is reduced: the pieces, the per-lane sums (exact_rows_sum), the butterfly and the keys
+// (exact_rows_keys).
+template <int NB, int MP>
+__device__ __forceinline__ void exact_rows_load(const float* __restrict__ X, int G, int np, const uint32_t* rows,
+                                                int nb, f32x4 (&xv)[MP][NB]) {
     const int lane = threadIdx.x & 63;
     const int Dp = G * GROUP_DIMS;
-    f32x4 xv[MP][NB];
 #pragma unroll
     for (int m = 0; m < MP; ++m) {
         const int p = m * 64 + lane;
@@ -34,7 +35,10 @@ __device__ __forceinline__ void exact_keys_regs(const float (&qv)[MP][4], double
             xv[m][u] = (m < np && u < nb && 4 * p < Dp) ? *(const f32x4*)(X + row_piece_offset(rows[u], p, G))
                                                        : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    double acc[NB];
+}
+template <int METRIC, int NB, int MP>
+__device__ __forceinline__ void exact_rows_sum(const float (&qv)[MP][4], const f32x4 (&xv)[MP][NB], int np,
+                                               double (&acc)[NB]) {
 #pragma unroll
     for (int u = 0; u < NB; ++u) acc[u] = 0.0;
 #pragma unroll
@@ -55,6 +59,49 @@ __device__ __forceinline__ void exact_keys_regs(const float (&qv)[MP][4], double
                 }
         }
     }
+}
+// (the same sums, in the order of exact_keys_rows of vdb_exact_keys.h, with the query's pieces read
+// from memory -- L1-resident -- per batch instead of held across batches: the 8-wave form's rows)
+template <int METRIC, int NB, int MP>
+__device__ __forceinline__ void exact_rows_sum_mem(const float* __restrict__ q, int D, const f32x4 (&xv)[MP][NB],
+                                                   int np, double (&acc)[NB]) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int u = 0; u < NB; ++u) acc[u] = 0.0;
+    // every piece's loads first and unconditional, an element past the row's end reading the
+    // row's last: behind a predicate each was a load and a wait of its own, 32 dependent (L1)
+    // trips a batch at C3
+    float qa[MP][4];
+#pragma unroll
+    for (int m = 0; m < MP; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int d = 4 * (m * 64 + lane) + j;
+            const float v = q[min(d, D - 1)];
+            qa[m][j] = d < D ? v : 0.0f;
+        }
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        if (m < np) {
+            const float (&qv)[4] = qa[m];
+#pragma unroll
+            for (int u = 0; u < NB; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double qd = (double)qv[j];
+                    const double xd = (double)xv[m][u][j];
+                    if (METRIC == 0) {
+                        acc[u] = acc[u] + qd * xd;
+                    } else {
+                        const double df = xd - qd;
+                        acc[u] = acc[u] + df * df;
+                    }
+                }
+        }
+    }
+}
+template <int METRIC, int NB>
+__device__ __forceinline__ void exact_rows_keys(double (&acc)[NB], double qn, const double* xn, int nb, double* out) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1)
 #pragma unroll
@@ -200,13 +247,14 @@ __device__ unsigned long long g_fin_stamps[8192][16];
 // FW waves per workgroup: 16 (FIN_WAVES), or 8 for rows of more than 1024 dims (no spills at the
 // 8-piece exact keys: C3 400-413 K -> 419-421 K QPS; C2 / C4 / C6 -0.5..-1% at 8, so they keep 16;
 // profiles/r05_ab/ab34_finish_waves.log)
-// The small form (FW = 4, CAP = FIN_CAP_SMALL: 4 waves of <= 128 VGPRs, ~45 KiB of LDS) fits beside a
+// The small form (FW = 4, CAP = FIN_CAP_SMALL: 4 waves of <= 168 VGPRs, ~51 KiB of LDS, so three
+// workgroups a CU at the most: the launch bound) fits beside a
 // long-row wide scan workgroup (vdb_scan8wl.hip: 8 waves of 170 VGPRs, 98 KiB of LDS at 768 dims),
 // so under several streams a batch's finish runs beside the next batch's scan instead of after it;
 // a list longer than CAP goes to the exact path.
 constexpr int FIN_CAP_SMALL = 4096;
 template <int METRIC, int KP, int FW = FIN_WAVES, int CAP = FIN_CAP>
-__global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(FinishArgs a) {
+__global__ void __launch_bounds__(64 * FW, FW <= 4 ? 3 : 1) finish_kernel(FinishArgs a) {
     constexpr int FIN_WAVES = FW;  // (shadows the default inside this kernel)
     constexpr int FIN_NB4 = FW > 8 || FW <= 4 ? 3 : 6;
     constexpr int FIN_CAP = CAP;   // (likewise)
@@ -227,15 +275,86 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
     const int S = a.split, sp = blockIdx.y;  // split > 1: S workgroups per query share the rerank
     if (a.gate && b >= *a.gate) return;  // device re-pass: a slot past the gathered count
     FIN_STAMP(0);
+    // Every per-query value a later phase reads is requested here, ahead of the list load, and
+    // published in LDS at the barrier that ends the list load: the first thread of the last wave
+    // takes the scalars (wave 0 has the checksum's words to fetch), every thread its elements of
+    // the query row (the exact keys' register path) and of the rounding residual (the
+    // refinement's).  Each of them was a dependent round trip of its own behind a barrier of the
+    // certificate, the refinement or the exact keys; beside two scans such a trip costs several
+    // times its stand-alone 2 us.  (The scalars' addresses are uniform, so they compile to
+    // scalar loads that the one thread waits for at once, *chkr after the others: two short
+    // trips of the last wave beside wave 0's, not under the list load.)
+    // launch_finish runs the 16- and 4-wave forms for D <= 1024 alone (when the default form has
+    // more than 8 waves), so they compile the register path only: 212 -> 0 bytes of scratch per
+    // lane, c4 shard +1.5% (profiles/r06_nosp; the 8-wave form keeps every path: pruned, C3 -1%)
+    constexpr bool kShortOnly = FW != 8 && VDB_FIN_WAVES > 8;
+    // The copies are sized by the rows a form is launched with.  The query row: 1024 dims in the
+    // 4- and 16-wave forms; none in the 8-wave form, whose rows (D > 1024 in the default build)
+    // take exact_keys_rows, which reads the query from memory as it goes.  The residual: 1024
+    // dims, or VDB_FIN_RES8 in the 8-wave form (C3: 1536; longer rows read it from memory).
+#ifndef VDB_FIN_RES8
+#define VDB_FIN_RES8 2048
+#endif
+    constexpr bool kStageQ = FW != 8;
+    constexpr int QLQ = kStageQ ? 1024 : 0, QLR = FW == 8 ? VDB_FIN_RES8 : 1024;
+    constexpr int NQQ = QLQ / (64 * FW), NQR = QLR / (64 * FW);
+    static_assert(QLQ % (64 * FW) == 0 && QLR % (64 * FW) == 0, "whole turns of the workgroup");
+    __shared__ __attribute__((aligned(16))) float s_q[QLQ > 0 ? QLQ : 4];
+    __shared__ __attribute__((aligned(16))) float s_res[QLR > 0 ? QLR : 4];
+    __shared__ double s_qn, s_qc[3];
+    __shared__ float s_qe, s_qe2, s_qsc;
+    __shared__ uint32_t s_chkr;
+    const bool r_lds = QLR > 0 && a.xh_rm != nullptr && a.qres != nullptr && (kShortOnly || a.Dp <= QLR);
+    float t_q[NQQ > 0 ? NQQ : 1], t_r[NQR > 0 ? NQR : 1];
+#pragma unroll
+    for (int i = 0; i < NQQ; ++i) {
+        const int d = tid + 64 * FW * i;
+        t_q[i] = d < a.D ? a.Q[(int64_t)b * a.D + d] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < NQR; ++i) {
+        const int d = tid + 64 * FW * i;
+        t_r[i] = r_lds && d < a.Dp ? a.qres[(size_t)b * a.Dp + d] : 0.0f;
+    }
+    double t_qn = 0.0, t_qc[3] = {0.0, 0.0, 0.0};
+    float t_qe = 0.0f, t_qe2 = 0.0f, t_qsc = 0.0f;
+    uint32_t t_chkr = 0u;
+    constexpr int kScalarTid = 64 * (FW - 1);
+    if (tid == kScalarTid) {
+        t_qn = a.qn64[b];
+        if (a.qconst) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) t_qc[i] = a.qconst[3 * (size_t)b + i];
+        }
+        if (a.qerr) t_qe = a.qerr[b];
+        if (a.qerr2) t_qe2 = a.qerr2[b];
+        if (a.xh_rm && a.qscal) t_qsc = a.qscal[0];
+        if (a.chkp && a.chkr) t_chkr = *a.chkr;
+    }
     // The int8 pass's checksum (vdb_scan8.hip): the workgroups' partial sums of this query's H (and
     // L) accumulators ([plane][query][workgroup], one coalesced read per lane), loaded here and
     // compared at the end against the value the stored operands imply.
     __shared__ int s_ckbad;
     uint32_t ck_h = 0u, ck_l = 0u, ck_eh = 0u, ck_el = 0u;
     if (a.chkp && tid < 64) {
-        for (int w = tid; w < a.chk_nw; w += 64) {
-            ck_h += a.chkp[(size_t)b * a.chk_nw + w];
-            if (a.chk_l) ck_l += a.chkp[((size_t)a.chk_ld + b) * a.chk_nw + w];
+        // (four words per lane requested together: with one per turn, the usual 256 workgroups
+        // were four dependent round trips of wave 0 ahead of the first barrier; the sums are
+        // integers modulo 2^32, so the order of the additions does not matter)
+        for (int w0 = tid; w0 < a.chk_nw; w0 += 256) {
+            uint32_t h4[4], l4[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int w = min(w0 + 64 * u, a.chk_nw - 1);  // (past the end: the last word again, not added)
+                h4[u] = a.chkp[(size_t)b * a.chk_nw + w];
+                l4[u] = a.chk_l ? a.chkp[((size_t)a.chk_ld + b) * a.chk_nw + w] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (w0 + 64 * u < a.chk_nw) {
+                    ck_h += h4[u];
+                    ck_l += l4[u];
+                }
+            }
         }
         if (a.chke && tid == 0) {  // the expectations the pilot computed
             ck_eh = a.chke[2 * (size_t)b];
@@ -289,11 +408,13 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
     // leaves about KP entries.
     const uint32_t tkey = a.gthr[b];
     __shared__ int s_n, s_ovf;
+    __shared__ uint32_t s_cbmax;  // the refinement's largest per-row rounding bound (zeroed here: no barrier of its own)
     if (tid == 0) {
         s_ak = 0;
         s_akp = 0;
         s_n = 0;
         s_ovf = 0;
+        s_cbmax = 0u;
     }
     __syncthreads();
     // the wide int8 pass's lists: one segment of W8_CH slots per scan workgroup, wave wv taking
@@ -303,7 +424,22 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
     // one wave per segment took a dependent round trip per segment, 32 per wave at C3 / C4)
     for (int sg0 = a.seg_cnt ? wv * 64 : a.seg_n; sg0 < a.seg_n; sg0 += FIN_WAVES * 64) {
         const int sg = sg0 + lane;
-        uint32_t cnt = sg < a.seg_n ? a.seg_cnt[(size_t)b * a.seg_n + sg] : 0u;
+        const bool sin = sg < a.seg_n;
+        uint32_t cnt = sin ? a.seg_cnt[(size_t)b * a.seg_n + sg] : 0u;
+        // the segment's first four entry slots with its count (slots past the count hold stale
+        // entries, masked below; all inside the segment, W8_CH >= 4): the usual segment of at most
+        // four entries is one round trip instead of two
+        // (an address of the query's own lists for every lane, a lane past the last segment
+        // reading segment 0, so that the loads are unconditional: behind a predicate the compiler
+        // moved them to their uses, after the wait for the count)
+        const size_t sg_at = sin ? (size_t)sg * W8_CH : 0;
+        const f32x4 f0 = *(const f32x4*)(ls + sg_at);
+        uint4 r4 = *(const uint4*)(li + sg_at);
+        uint32_t k0[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) k0[u] = order_key(f0[u]);
+        asm volatile("" : "+v"(r4.x), "+v"(r4.y), "+v"(r4.z), "+v"(r4.w));  // (the rows' use, here: see above)
+        const uint32_t r0[4] = {r4.x, r4.y, r4.z, r4.w};
         if (cnt > (uint32_t)W8_CH) {
             s_ovf = 1;
             cnt = 0;
@@ -316,8 +452,13 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
 #pragma unroll
             for (int u = 0; u < 4; ++u) {  // (four entry slots' loads in flight together)
                 const bool in = j + u < cnt;
-                key[u] = in ? order_key(ls[(size_t)sg * W8_CH + j + u]) : 0u;
-                row[u] = in ? li[(size_t)sg * W8_CH + j + u] : 0u;
+                if (j == 0) {
+                    key[u] = in ? k0[u] : 0u;
+                    row[u] = in ? r0[u] : 0u;
+                } else {
+                    key[u] = in ? order_key(ls[(size_t)sg * W8_CH + j + u]) : 0u;
+                    row[u] = in ? li[(size_t)sg * W8_CH + j + u] : 0u;
+                }
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -350,6 +491,20 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
             s_key[pos] = key;
             s_row[pos] = row;
         }
+    }
+    // publish the values requested at the top
+#pragma unroll
+    for (int i = 0; i < NQQ; ++i) s_q[tid + 64 * FW * i] = t_q[i];
+#pragma unroll
+    for (int i = 0; i < NQR; ++i) s_res[tid + 64 * FW * i] = t_r[i];
+    if (tid == kScalarTid) {
+        s_qn = t_qn;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) s_qc[i] = t_qc[i];
+        s_qe = t_qe;
+        s_qe2 = t_qe2;
+        s_qsc = t_qsc;
+        s_chkr = t_chkr;
     }
     __syncthreads();
     if (s_ovf || s_n > FIN_CAP) {  // (uniform: every thread returns)
@@ -470,7 +625,34 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
     __syncthreads();
     FIN_STAMP(2);
     int m = s_m;
-    const double qn = a.qn64[b];
+    const double qn = s_qn;
+    // The I8 refinement's row loads (below, after the certificate), two batches of NBR rows per
+    // wave in flight: batch t + 1 is requested before batch t is reduced, and batch 0 here, as
+    // soon as the selection is final, so the rank counts and the certificate run under it.  Only
+    // rows s_cr[j], j < m, of a query that has its k candidates are requested (fewer: the
+    // certificate sets no cut and there is no refinement); where the certificate then sets no cut
+    // after all, the values are dropped.  Step t = (batch, 1024-dim chunk of the row).
+#ifndef VDB_FIN_NBR
+#define VDB_FIN_NBR (FIN_WAVES > 8 ? 4 : 8)
+#endif
+    constexpr int NBR = VDB_FIN_NBR;  // candidates per wave per batch (row loads in flight together)
+    const int rf_nch = kShortOnly ? 1 : (a.Dp + 1023) >> 10;
+    const int rf_T = a.xh_rm != nullptr && m >= a.k && m > wv * NBR
+                         ? (m - wv * NBR + FIN_WAVES * NBR - 1) / (FIN_WAVES * NBR) * rf_nch : 0;
+    // A step's NBR loads are unconditional (t < rf_T, the wave's own step): behind per-load
+    // predicates the compiler cannot count what is in flight and waits for everything, the batch
+    // just requested included.  The last batch's slots past m repeat candidate m - 1 and a lane
+    // past the row's end its first 16 bytes: addresses of validated rows, values never used.
+    auto rf_issue = [&](int t, f32x4 (&xv)[NBR]) {
+        const int bi = rf_nch == 1 ? t : t / rf_nch;
+        const int j0 = (wv + FIN_WAVES * bi) * NBR, off = (t - bi * rf_nch) * 1024 + 16 * lane;
+        const int offc = off < a.Dp ? off : 0;
+#pragma unroll
+        for (int u = 0; u < NBR; ++u)
+            xv[u] = *(const f32x4*)(a.xh_rm + (size_t)s_cr[min(j0 + u, m - 1)] * a.Dp + offc);
+    };
+    f32x4 rf_xa[NBR], rf_xb[NBR];
+    if (rf_T > 0) rf_issue(0, rf_xa);
     // ---- the certificate first, from the approximate scores alone ----
     // a_k / a_KP: the k-th / KP-th best approx key of the selection (rank counting, TPC threads
     // per candidate).  Rows outside the candidates scored (approx) <= acut = max(a_KP, T)
@@ -524,7 +706,7 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
         // test compares an exact key with them.
         double mq = 0.0;
         if (a.mu && a.qconst) {
-            mq = a.qconst[3 * (size_t)b];
+            mq = s_qc[0];
         } else if (a.mu) {
             const float* qq = a.Q + (int64_t)b * a.D;
             const double qs = METRIC == 0 ? 1.0 / fmax(qn, 1e-8) : 1.0;
@@ -540,8 +722,8 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
             if (a.dir) {
                 double c = 0.0, w2 = 0.0;
                 if (a.qconst) {
-                    c = a.qconst[3 * (size_t)b + 1];
-                    w2 = a.qconst[3 * (size_t)b + 2];
+                    c = s_qc[1];
+                    w2 = s_qc[2];
                 } else {
                     const float* qq = a.Q + (int64_t)b * a.D;
                     const double qs = METRIC == 0 ? 1.0 / fmax(qn, 1e-8) : 1.0;
@@ -600,15 +782,15 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
     FIN_STAMP(15);
     if (tid == 0) {
         if (a.chkp) {
-            const uint32_t eh = (a.chke ? ck_eh : s_ckeh) + (a.chkr ? *a.chkr : 0u);
+            const uint32_t eh = (a.chke ? ck_eh : s_ckeh) + s_chkr;
             const uint32_t el = a.chke ? ck_el : s_ckel;
             s_ckbad = ck_h != eh || (a.chk_l && ck_l != el);
         }
         const bool full = m == KP;
-        const double T = (double)key_to_float(a.gthr[b]);
+        const double T = (double)key_to_float(tkey);
         const bool have_k = m >= a.k;
         const double ak = have_k ? (double)key_to_float(s_ak) : -INFINITY;
-        const double qe = a.qerr ? (double)a.qerr[b] : 0.0;  // the int8 pass's per-query share
+        const double qe = (double)s_qe;  // the int8 pass's per-query share (0 without one)
         bool ok = true;
         double eps = 0.0;
         if (full || T > -INFINITY) {
@@ -662,82 +844,106 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
     if (threadIdx.x == 0) g_fin_stamps[blockIdx.x][6] = __builtin_amdgcn_s_memtime();
 #endif
     __shared__ __attribute__((aligned(16))) float s_ca[KP];
-    __shared__ uint32_t s_cbmax;
     __shared__ float s_ak2;
     __shared__ double s_e2;  // the refined bound eps' (the consistency guard checks a' against it too)
     const bool refine = a.xh_rm != nullptr && s_cut > -INFINITY;
     if (refine) {
-        if (tid == 0) s_cbmax = 0u;
-        __syncthreads();
-#ifndef VDB_FIN_NBR
-#define VDB_FIN_NBR (FIN_WAVES > 8 ? 4 : 8)
-#endif
-        constexpr int NBR = VDB_FIN_NBR;  // candidates per wave per batch (row loads in flight together)
-        const float* rq = a.qres + (size_t)b * a.Dp;
         const float fsx = (METRIC == 0 ? 1.0f : 2.0f) * a.sx;
-        const float qmx = 127.0f * a.qscal[0] / a.sx;  // s_q * 127 = max |q'|
-        // the rows are stored as u = xh + 128: xh.r = u.r - 128 sum(r); sum(r) and sum|r| once
-        float rsum = 0.0f, rabs = 0.0f;
-        for (int off = 16 * lane; off < a.Dp; off += 1024)
+        const float qmx = 127.0f * s_qsc / a.sx;  // s_q * 127 = max |q'|
+        // rd(o): 16 bytes of the residual at element o, from the LDS copy made at the top or, rows
+        // of more than QLR dims, from memory: one instance of the loops each (a pointer chosen at run
+        // time makes them flat loads, which wait for every vector load in flight)
+        auto rf_run = [&](auto rd) {
+            // the rows are stored as u = xh + 128: xh.r = u.r - 128 sum(r); sum(r) and sum|r| once
+            float rsum = 0.0f, rabs = 0.0f;
+            for (int off = 16 * lane; off < a.Dp; off += 1024)
 #pragma unroll
-            for (int w4 = 0; w4 < 4; ++w4) {
-                const f32x4 rv = *(const f32x4*)(rq + off + 4 * w4);
+                for (int w4 = 0; w4 < 4; ++w4) {
+                    const f32x4 rv = rd(off + 4 * w4);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    rsum += rv[e];
-                    rabs += fabsf(rv[e]);
+                    for (int e = 0; e < 4; ++e) {
+                        rsum += rv[e];
+                        rabs += fabsf(rv[e]);
+                    }
                 }
-            }
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            rsum += __shfl_xor(rsum, off, 64);
-            rabs += __shfl_xor(rabs, off, 64);
-        }
-        // fp32 bound of the correction, per query: the D biased products and their sum (|u r|
-        // <= 256 |r|), the subtraction of 128 sum(r), r = q' - s_q qh itself (<= 2 ulp of |q'|
-        // per element), times f s_x; plus (per row) the roundings of a'
-        const float bq2 = fsx * (((float)a.Dp + 8.0f) * 5.97e-8f * 256.0f * rabs + 1.2e-7f * qmx * 127.0f * (float)a.D);
-        FIN_STAMP(8);
-        for (int j0 = wv * NBR; j0 < m; j0 += FIN_WAVES * NBR) {
+            for (int off = 32; off >= 1; off >>= 1) {
+                rsum += __shfl_xor(rsum, off, 64);
+                rabs += __shfl_xor(rabs, off, 64);
+            }
+            // fp32 bound of the correction, per query: the D biased products and their sum (|u r|
+            // <= 256 |r|), the subtraction of 128 sum(r), r = q' - s_q qh itself (<= 2 ulp of |q'|
+            // per element), times f s_x; plus (per row) the roundings of a'
+            const float bq2 = fsx * (((float)a.Dp + 8.0f) * 5.97e-8f * 256.0f * rabs + 1.2e-7f * qmx * 127.0f * (float)a.D);
+            FIN_STAMP(8);
+            // one step: the chunk's products added to the batch's sums in the order of `off`, and
+            // after the row's last chunk the butterfly and a' (the same operations per candidate in
+            // the same order whatever is in flight)
             float sum[NBR];
+            auto rf_step = [&](int t, const f32x4 (&xv)[NBR]) {
+                const int bi = rf_nch == 1 ? t : t / rf_nch, ci = t - bi * rf_nch;
+                const int j0 = (wv + FIN_WAVES * bi) * NBR, off = ci * 1024 + 16 * lane;
+                if (ci == 0) {
 #pragma unroll
-            for (int u = 0; u < NBR; ++u) sum[u] = 0.0f;
-            for (int off = 16 * lane; off < a.Dp; off += 1024) {
-                f32x4 xv[NBR];
-#pragma unroll
-                for (int u = 0; u < NBR; ++u)
-                    xv[u] = j0 + u < m ? *(const f32x4*)(a.xh_rm + (size_t)s_cr[j0 + u] * a.Dp + off)
-                                       : f32x4{0.f, 0.f, 0.f, 0.f};
-                f32x4 rv[4];
-#pragma unroll
-                for (int w4 = 0; w4 < 4; ++w4) rv[w4] = *(const f32x4*)(rq + off + 4 * w4);
-#pragma unroll
-                for (int u = 0; u < NBR; ++u)
-#pragma unroll
-                    for (int w4 = 0; w4 < 4; ++w4) {
-                        const uint32_t word = __float_as_uint(xv[u][w4]);
-#pragma unroll
-                        for (int bt = 0; bt < 4; ++bt)
-                            sum[u] = fmaf((float)((word >> (8 * bt)) & 255u), rv[w4][bt], sum[u]);
-                    }
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-                for (int u = 0; u < NBR; ++u) sum[u] += __shfl_xor(sum[u], off, 64);
-            if (lane == 0) {
-                float bmax = 0.0f;
-#pragma unroll
-                for (int u = 0; u < NBR; ++u) {
-                    const int j = j0 + u;
-                    if (j < m) {
-                        const float ap = key_to_float(s_ck[j]) + fsx * (sum[u] - 128.0f * rsum);
-                        s_ca[j] = ap;
-                        bmax = fmaxf(bmax, 2.4e-7f * fabsf(ap));
-                    }
+                    for (int u = 0; u < NBR; ++u) sum[u] = 0.0f;
                 }
-                atomicMax(&s_cbmax, __float_as_uint((bq2 + bmax) * 1.01f));
+                if (off < a.Dp) {
+                    f32x4 rv[4];
+#pragma unroll
+                    for (int w4 = 0; w4 < 4; ++w4)
+                        rv[w4] = rd(off + 4 * w4);
+#pragma unroll
+                    for (int u = 0; u < NBR; ++u)
+#pragma unroll
+                        for (int w4 = 0; w4 < 4; ++w4) {
+                            const uint32_t word = __float_as_uint(xv[u][w4]);
+#pragma unroll
+                            for (int bt = 0; bt < 4; ++bt)
+                                sum[u] = fmaf((float)((word >> (8 * bt)) & 255u), rv[w4][bt], sum[u]);
+                        }
+                }
+                if (ci != rf_nch - 1) return;
+#pragma unroll
+                for (int off2 = 32; off2 >= 1; off2 >>= 1)
+#pragma unroll
+                    for (int u = 0; u < NBR; ++u) sum[u] += __shfl_xor(sum[u], off2, 64);
+                if (lane == 0) {
+                    float bmax = 0.0f;
+#pragma unroll
+                    for (int u = 0; u < NBR; ++u) {
+                        const int j = j0 + u;
+                        if (j < m) {
+                            const float ap = key_to_float(s_ck[j]) + fsx * (sum[u] - 128.0f * rsum);
+                            s_ca[j] = ap;
+                            bmax = fmaxf(bmax, 2.4e-7f * fabsf(ap));
+                        }
+                    }
+                    atomicMax(&s_cbmax, __float_as_uint((bq2 + bmax) * 1.01f));
+                }
+            };
+            // (step 0 was requested before the certificate; the steady state requests unconditionally,
+            // so each wait leaves exactly the step just requested in flight, and the last one or two
+            // steps are taken without a request after them)
+            int t = 0;
+            for (; t + 2 < rf_T; t += 2) {
+                rf_issue(t + 1, rf_xb);
+                rf_step(t, rf_xa);
+                rf_issue(t + 2, rf_xa);
+                rf_step(t + 1, rf_xb);
             }
+            if (t + 2 == rf_T) {
+                rf_issue(t + 1, rf_xb);
+                rf_step(t, rf_xa);
+                rf_step(t + 1, rf_xb);
+            } else if (t + 1 == rf_T) {
+                rf_step(t, rf_xa);
+            }
+        };
+        if (kShortOnly || r_lds) {
+            rf_run([&](int o) { return *(const f32x4*)(s_res + o); });
+        } else {
+            const float* rq = a.qres + (size_t)b * a.Dp;
+            rf_run([&](int o) { return *(const f32x4*)(rq + o); });
         }
         FIN_STAMP(9);
         __syncthreads();
@@ -773,7 +979,7 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
         FIN_STAMP(11);
         if (tid == 0) {
             const double ak2 = (double)s_ak2;
-            const double qe2 = a.qerr2 ? (double)a.qerr2[b] : 0.0;
+            const double qe2 = (double)s_qe2;
             const double e2 = (METRIC == 0 ? a.eps_rel + s_bq + qe2
                                            : a.eps_rel * (2.0 * qn * a.xmax + a.xmax * a.xmax) + 2.0 * s_bq + qe2) +
                               (double)__uint_as_float(s_cbmax);
@@ -842,28 +1048,52 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
     const float* q = a.Q + (int64_t)b * a.D;
     // exact keys: wave wv takes candidates wv NB, ... in batches of NB
     const int np = (a.D + 255) / 256;
-    // the register path: the query's pieces held, NB rows' pieces loaded at once per batch
-    auto keys_regs = [&](auto mp_c, auto nb_c) {
+    // The batched paths (rows of up to 256 MP dims): every piece of NB rows requested at once.  HELD:
+    // the query's pieces in registers, from their LDS copy (the 4- and 16-wave forms); else read
+    // from memory (L1-resident) as each piece is consumed (the 8-wave form: C3's 8 pieces).
+    auto keys_ahead = [&](auto mp_c, auto nb_c, auto held_c) {
         constexpr int MP = decltype(mp_c)::value, NB = decltype(nb_c)::value;
-        float qv[MP][4];
-#pragma unroll
-        for (int mm = 0; mm < MP; ++mm)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int d = 4 * (mm * 64 + lane) + j;
-                qv[mm][j] = (mm < np && d < a.D) ? q[d] : 0.0f;
-            }
-        for (int j0 = wv * NB; j0 < mx; j0 += FIN_WAVES * NB) {
+        constexpr bool HELD = decltype(held_c)::value;
+        // a batch's norms and row pieces, requested together; the next batch's are requested once
+        // this batch's products are summed (its pieces' registers are free again), before its fp64
+        // butterfly, and the first batch before the query pieces are read
+        f32x4 xv[MP][NB];
+        double xnl = 1.0;  // row u's norm in lane u (one register pair for the batch)
+        auto issue = [&](int j0) {
+            const int nb = min(NB, mx - j0);  // (<= 0 past the wave's last batch: nothing is requested)
             uint32_t rows[NB];
-            double xn[NB];
-            const int nb = min(NB, mx - j0);
 #pragma unroll
-            for (int u = 0; u < NB; ++u) {
-                rows[u] = u < nb ? xr[j0 + u] : 0u;
-                xn[u] = (METRIC == 0 && u < nb) ? a.nrm64[rows[u]] : 1.0;
+            for (int u = 0; u < NB; ++u) rows[u] = u < nb ? xr[j0 + u] : 0u;
+            xnl = (METRIC == 0 && lane < nb) ? a.nrm64[xr[j0 + lane]] : 1.0;
+            exact_rows_load<NB, MP>(a.X, a.G, np, rows, nb, xv);
+        };
+        issue(wv * NB);
+        float qv[HELD ? MP : 1][4];
+        if (HELD) {
+#pragma unroll
+            for (int mm = 0; mm < (HELD ? MP : 0); ++mm) {
+                // (rows of at most 256 MP <= 1024 dims: the query is in s_q, zeros from D on)
+                const f32x4 ql = *(const f32x4*)(s_q + 4 * (mm * 64 + lane));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) qv[mm][j] = ql[j];
             }
+        }
+        // (the 16-wave form requests the next batch after the butterfly: beside it the pieces in
+        // flight cost 36 bytes of scratch per lane at its 128 registers, and with 48 rows a round
+        // few of its waves have a second batch at all)
+        constexpr bool kAhead = FIN_WAVES <= 8;
+        for (int j0 = wv * NB; j0 < mx; j0 += FIN_WAVES * NB) {
+            const int nb = min(NB, mx - j0);
+            if (!kAhead && j0 != wv * NB) issue(j0);
+            double acc[NB], xnc[NB];
+            if constexpr (HELD) exact_rows_sum<METRIC, NB, MP>(qv, xv, np, acc);
+            else exact_rows_sum_mem<METRIC, NB, MP>(q, a.D, xv, np, acc);
+            const double xnh = xnl;
+            if (kAhead) issue(j0 + FIN_WAVES * NB);
+#pragma unroll
+            for (int u = 0; u < NB; ++u) xnc[u] = __shfl(xnh, u, 64);
             double keys[NB];
-            exact_keys_regs<METRIC, NB, MP>(qv, qn, a.X, a.G, np, rows, xn, nb, keys);
+            exact_rows_keys<METRIC, NB>(acc, s_qn, xnc, nb, keys);
             if (lane == 0) {
 #pragma unroll
                 for (int u = 0; u < NB; ++u)
@@ -871,30 +1101,13 @@ __global__ void __launch_bounds__(64 * FW, FW <= 4 ? 4 : 1) finish_kernel(Finish
             }
         }
     };
-    // launch_finish runs the 16- and 4-wave forms for D <= 1024 alone (when the default form has
-    // more than 8 waves), so they compile the register path only: 212 -> 0 bytes of scratch per
-    // lane, c4 shard +1.5% (profiles/r06_nosp; the 8-wave form keeps every path: pruned, C3 -1%)
-    constexpr bool kShortOnly = FW != 8 && VDB_FIN_WAVES > 8;
+    // (kShortOnly, at the top: the 16- and 4-wave forms compile the register path only)
     if (kShortOnly || np <= FIN_MP) {
-        keys_regs(std::integral_constant<int, FIN_MP>{}, std::integral_constant<int, FIN_NB4>{});
+        keys_ahead(std::integral_constant<int, FIN_MP>{}, std::integral_constant<int, FIN_NB4>{},
+                   std::integral_constant<bool, kStageQ>{});
     } else if (np <= FIN_MP8) {
-        for (int j0 = wv * FIN_NB8; j0 < mx; j0 += FIN_WAVES * FIN_NB8) {
-            uint32_t rows[FIN_NB8];
-            double xn[FIN_NB8];
-            const int nb = min(FIN_NB8, mx - j0);
-#pragma unroll
-            for (int u = 0; u < FIN_NB8; ++u) {
-                rows[u] = u < nb ? xr[j0 + u] : 0u;
-                xn[u] = (METRIC == 0 && u < nb) ? a.nrm64[rows[u]] : 1.0;
-            }
-            double keys[FIN_NB8];
-            exact_keys_rows<METRIC, FIN_NB8, FIN_MP8>(q, a.D, qn, a.X, a.G, np, rows, xn, nb, keys);
-            if (lane == 0) {
-#pragma unroll
-                for (int u = 0; u < FIN_NB8; ++u)
-                    if (u < nb) xek[j0 + u] = keys[u];
-            }
-        }
+        keys_ahead(std::integral_constant<int, FIN_MP8>{}, std::integral_constant<int, FIN_NB8>{},
+                   std::integral_constant<bool, false>{});
     } else if (!kShortOnly)
     for (int j0 = wv * FIN_NB; j0 < mx; j0 += FIN_WAVES * FIN_NB) {
         uint32_t rows[FIN_NB];
