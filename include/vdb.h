@@ -153,7 +153,8 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * search fetches, 0 = auto, 1..200) and "group_force_exact" (0/1; its stats "group_rows",
  * "group_sets", "group_searches", "group_queries", "group_fallback_queries" are described
  * there; vdb_index_search_mmr's are "mmr_searches", "mmr_queries"; vdb_index_search_recommend's
- * "recommend_searches", "recommend_queries", "recommend_bad_queries").  Stats also: "searches", "queries",
+ * "recommend_searches", "recommend_queries", "recommend_bad_queries"; vdb_index_search_fused's
+ * "fused_searches", "fused_sets", "fused_bad_sets").  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -493,6 +494,79 @@ int32_t vdb_index_search_recommend(vdb_index* idx, int32_t n_queries, int32_t k,
                                    const uint32_t* row_mask, int32_t mem,
                                    float* out_scores, int64_t* out_indices, double* out_keys, float* out_queries,
                                    int64_t index_offset, void* stream);
+
+/* --- fused search: one ranked list from several query vectors ----------------------
+ * Replaces: nothing the reference has.  Its RAG pipeline retrieves with one embedding of the
+ * question (integrations/mlx_lm_pipeline.py); the usual next step is several per question
+ * (paraphrases, the question plus a hypothetical answer, a title and a body embedding) answered
+ * with one list, as Milvus' hybrid_search with RRFRanker, Qdrant's prefetch + fusion and LangChain's
+ * EnsembleRetriever do.  Without this call a user runs a batch search, pulls the lists to the host
+ * and adds reciprocal ranks in a dict: the sums tie exactly all the time, so the order depends on
+ * an unstated tie rule, and a device-memory caller cannot do it at all.
+ *
+ *   queries      [n_sub, dim] fp32: the sub-queries of all sets, back to back
+ *   set_offsets  [n_sets + 1] int64, CSR as vdb_index_search_rows' lists: set s is sub-queries
+ *                [set_offsets[s], set_offsets[s + 1]).  A set has 0..16 sub-queries; one without
+ *                any is no error, all its slots are "no result".
+ *   n_sub        host scalar: the launches are sized from it, so a device-memory call reads nothing
+ *                back
+ *   weights      NULL, or [n_sub] fp64, one per sub-query, finite and >= 0.  NULL is 1.0 for RRF; it
+ *                must be NULL for VDB_FUSE_MAX.
+ *   k, fetch_k   1 <= k <= fetch_k <= 200 (the most the certified fast path returns, as for MMR)
+ *   fusion       VDB_FUSE_RRF or VDB_FUSE_MAX
+ *   rrf_c        host fp64, finite and >= 0 (customarily 60); ignored for MAX
+ *   out_scores / out_indices: [n_sets, k]; out_fused: NULL or [n_sets, k] fp64; out_hits: NULL or
+ *                [n_sets, k] int32
+ *   row_mask, mem, index_offset, stream: as vdb_index_search; all pointers of one memory kind.
+ *                n_sets == 0 is VDB_OK.
+ * Lists: list l of a set (l counted within the set, in sub-query order) is what vdb_index_search(k
+ * = fetch_k, row_mask) returns for that sub-query: rows c_{l,0} .. c_{l,n_l-1} by (canonical key
+ * desc, row asc) with keys kappa_{l,p}, n_l = min(fetch_k, eligible rows).  The candidates of a set
+ * are the union of its lists' rows; hits(r) is the number of lists holding r.
+ * RRF: fused(r) in fp64, every operation separate: acc = 0.0; for l ascending, if r stands in list l
+ * at position p: t = rrf_c + (double)(p + 1); u = w_l / t; acc = acc + u.
+ * MAX: fused(r) starts as the kappa of the first list (lowest l) holding r; for every later holding
+ * list fused = (kappa > fused) ? kappa : fused (this form and not fmax, so that the sign of a zero
+ * cannot differ between device and oracle).
+ * Ranking: candidates by (fused desc, row id asc); the first min(k, candidates) are written:
+ * out_indices = row id + index_offset, out_fused = fused, out_hits = hits, out_scores = (float)fused
+ * (round to nearest even) for RRF and, for MAX, the inner search's fp32 score at the list entry that
+ * holds the maximum (equal keys have equal scores, so which entry does not matter).  Slots past that
+ * hold index -1 / score 0 / fused -inf / hits 0.
+ * MAX is exact over the corpus: with fetch_k >= k the result is the top k of max_l key(q_l, r) over
+ * all eligible rows.  Take a row r of that top k and the list l where it attains its maximum: every
+ * row ahead of r in list l has a key there not below r's maximum, so its own maximum is not below
+ * r's, and at equality its row id is lower; so it is ahead of r in the fused order too.  Fewer than
+ * k rows are ahead of r in the fused order, hence fewer than k in that list: r is in the list.
+ * Consequences: a set of one sub-query under MAX with fetch_k == k returns, byte for byte,
+ * vdb_index_search(k) with out_fused = its out_keys.  The result of a set depends only on its own
+ * sub-queries.  The result is the same bytes for every precision setting and both memory kinds: the
+ * inner search is certified exact, and the fusion reads only its lists.
+ * How: the inner search fetches the lists of all n_sub sub-queries into scratch; one kernel, one
+ * workgroup per set, sorts the set's <= 3 200 list entries by (row, list) in LDS, lets the thread at
+ * the head of each row's run add that row's terms in list order, and sorts the candidates by (fused
+ * desc, row asc).  No sum depends on arrival order.
+ * Errors, before anything is launched, both memory kinds: k outside [1, 200], fetch_k outside [k,
+ * 200], an unknown fusion, rrf_c NaN / infinite / negative (RRF), a bad mem, n_sub or n_sets < 0, a
+ * NULL queries with n_sub > 0, a NULL set_offsets / out_scores / out_indices with n_sets > 0,
+ * weights with MAX -> VDB_ERR_INVALID.  Host-memory calls also: offsets that decrease or pass
+ * n_sub, a set of more than 16, a weight that is NaN, infinite or negative -> VDB_ERR_INVALID; a NaN
+ * or Inf in a query -> VDB_ERR_NONFINITE (no stat moves).  Device-memory calls are stream-ordered
+ * and read nothing back, so the kernel handles bad input itself: offsets are clamped to [0, n_sub]
+ * and nothing out of bounds is read; a set whose offsets decrease or lie outside [0, n_sub], that is
+ * longer than 16 or has a bad weight is answered with all slots "no result" and counted on the
+ * device in stat "fused_bad_sets"; the other sets of the call are unaffected.
+ * Takes the index's shared lock and a per-search workspace, as vdb_index_search_mmr does.  An empty
+ * index gives every slot "no result".  Stats (cumulative, successful calls): "fused_searches",
+ * "fused_sets", "fused_bad_sets"; "searches" / "queries" (+ n_sub) move once per call through the
+ * inner search. */
+enum { VDB_FUSE_RRF = 0, VDB_FUSE_MAX = 1 };
+int32_t vdb_index_search_fused(vdb_index* idx, const float* queries, int32_t n_sub,
+                               const int64_t* set_offsets, int32_t n_sets, const double* weights,
+                               int32_t k, int32_t fetch_k, int32_t fusion, double rrf_c,
+                               const uint32_t* row_mask, int32_t mem,
+                               float* out_scores, int64_t* out_indices, double* out_fused, int32_t* out_hits,
+                               int64_t index_offset, void* stream);
 
 /* --- multi-GPU merge -----------------------------------------------------------
  * Merge per-shard top-k lists (all device memory, already all-gathered):

@@ -79,6 +79,24 @@ class VectorMMRQuery(VectorQuery):
     lambda_mult: float = Field(default=0.5, description="1 = relevance only, 0 = diversity only")
 
 
+class VectorFusedQuery(BaseModel):
+    """One ranked list from several query vectors (paraphrases of a question, the question plus a
+    hypothetical answer, ...): each vector's best ``fetch_k`` rows (null: min(200, max(k, 4 k))) are
+    fused per row, ``fusion`` "rrf": the sum of ``weights[l] / (rrf_c + rank)`` over the lists holding
+    it, "max": its best match to any of the vectors.  The store checks the limits (at most 16
+    vectors, k and fetch_k at most 200, fetch_k >= k, weights finite and >= 0 and only with "rrf");
+    a value outside them is a 400."""
+    user_id: str
+    model_id: str
+    queries: List[List[float]] = Field(..., description="The query vectors fused into one list")
+    k: int = Field(default=10, description="Rows returned")
+    fusion: str = Field(default="rrf", description='"rrf" (weighted reciprocal rank) or "max" (best match to any)')
+    weights: Optional[List[float]] = Field(default=None, description="One weight per query vector (rrf only)")
+    fetch_k: Optional[int] = Field(default=None, description="Rows fetched per query vector")
+    rrf_c: float = Field(default=60.0, description="The constant added to a rank (rrf)")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+
+
 class VectorRecommendQuery(BaseModel):
     """Rows like the stored examples ``positive`` and unlike ``negative``: row indices, or with
     ``key`` (a metadata field, e.g. "doc_id") values of that field, every row holding one of them an
@@ -169,6 +187,15 @@ class VectorQueryResponse(BaseModel):
 class VectorRangeQueryResponse(BaseModel):
     results: List[Dict[str, Any]]
     total_matches: int  # the exact number of rows within the threshold; may exceed len(results)
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorFusedQueryResponse(BaseModel):
+    # best first: {"metadata", "fused_score", "hits", "rank"}; with fusion "max" also /vectors/query's
+    # "similarity_score" and "distance" of the best-matching vector
+    results: List[Dict[str, Any]]
+    fusion: str
     query_time_ms: float
     total_vectors_searched: int
 
@@ -434,6 +461,42 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in MMR query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"MMR query failed: {e}")
+
+    @router.post("/fused_query", response_model=VectorFusedQueryResponse)
+    async def fused_query_vectors(request: VectorFusedQuery, api_key: str = Depends(auth)):
+        """One ranked list from several query vectors, fused by weighted reciprocal rank or by the
+        best match to any of them.  A bad request (no vector, more than 16, k / fetch_k / rrf_c /
+        weights outside their limits, an unknown fusion, dimension mismatch: the store's ValueError)
+        is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if not request.queries or not all(request.queries):
+                raise HTTPException(status_code=400, detail="Query vectors required")
+            loop = asyncio.get_running_loop()
+            indices, scores, metas, fused, hits = await loop.run_in_executor(
+                mgr._executor, lambda: store.fused_query(request.queries, k=request.k, fusion=request.fusion,
+                                                         weights=request.weights, fetch_k=request.fetch_k,
+                                                         rrf_c=request.rrf_c, filter_metadata=request.filter_metadata))
+            if request.fusion == "max":
+                results = format_query_results(store.config.metric, indices, scores, metas)
+            else:
+                results = [{"metadata": m, "rank": i + 1} for i, m in enumerate(metas)]
+            for r, f, h in zip(results, fused, hits):
+                r["fused_score"] = f
+                r["hits"] = h
+            return VectorFusedQueryResponse(results=results, fusion=request.fusion,
+                                            query_time_ms=(time.time() - t0) * 1000,
+                                            total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Fused query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Fused query failed: {e}")
+        except Exception as e:
+            logger.error("Error in fused query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Fused query failed: {e}")
 
     @router.post("/recommend", response_model=VectorQueryResponse)
     async def recommend_vectors(request: VectorRecommendQuery, api_key: str = Depends(auth)):

@@ -28,6 +28,7 @@
 #include "vdb_range_plan.h"
 #include "vdb_group_plan.h"
 #include "vdb_mmr_plan.h"
+#include "vdb_fuse_plan.h"
 #include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
 #include "vdb_internal.h"
@@ -61,6 +62,7 @@ constexpr int64_t kRowAlign = ROW_ALIGN;   // capacity granule, a multiple of ev
 constexpr size_t kGatedExactBytes = 256u << 20;  // device-gated fallback lists sized for every query of a batch
 constexpr int kSubsetBadWord = 12;        // d_xmax word (8 bytes each) counting a row-list search's skipped ids
 constexpr int kRecommendBadWord = 13;     // d_xmax word counting the queries a recommend search flagged on the device
+constexpr int kFusedBadWord = 14;         // d_xmax word counting the sets a fused search found bad on the device
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 inline int next_pow2(int v) {
@@ -256,6 +258,9 @@ struct vdb_index {
     // vdb_index_search_recommend: calls and queries (successful calls); the queries its build kernel
     // flagged are counted on the device (d_xmax + kRecommendBadWord)
     std::atomic<int64_t> n_rec_searches{0}, n_rec_queries{0};
+    // vdb_index_search_fused: calls and sets (successful calls); the sets its kernel found bad are
+    // counted on the device (d_xmax + kFusedBadWord)
+    std::atomic<int64_t> n_fused_searches{0}, n_fused_sets{0};
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -864,7 +869,8 @@ int32_t vdb_index_create(int32_t dim, int32_t metric, int32_t device, vdb_index*
     // d_xmax: [0, 32) the residual maxima, [32, 36) the non-finite count, [64, 96) and
     // [128, 192) an add's snapshot of the maxima and of d_i8 (restored when the add is rejected),
     // [96, 104) the ids row-list searches skipped (kSubsetBadWord; cumulative, a clear keeps it),
-    // [104, 112) the queries recommend searches flagged (kRecommendBadWord; likewise)
+    // [104, 112) the queries recommend searches flagged (kRecommendBadWord; likewise),
+    // [112, 120) the sets fused searches found bad (kFusedBadWord; likewise)
     if (e == hipSuccess) e = hipMalloc(&ix->d_xmax, 192);
     if (e == hipSuccess) e = zero_now(ix->d_xmax, 192, ix->stream);
     if (e == hipSuccess) e = hipMalloc(&ix->d_i8, 64);
@@ -1172,6 +1178,16 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
         if (wr) return wr;
         unsigned long long bad = 0;
         HIP_TRY(hipMemcpy(&bad, ix->d_xmax + kRecommendBadWord, sizeof(bad), hipMemcpyDeviceToHost));
+        *value = (int64_t)bad;
+    }
+    else if (n == "fused_searches") *value = ix->n_fused_searches.load();
+    else if (n == "fused_sets") *value = ix->n_fused_sets.load();
+    else if (n == "fused_bad_sets") {  // counted by the fuse kernel: after the searches queued so far
+        HIP_TRY(hipSetDevice(ix->device));
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpy(&bad, ix->d_xmax + kFusedBadWord, sizeof(bad), hipMemcpyDeviceToHost));
         *value = (int64_t)bad;
     }
     else if (n == "group_fallback_queries") {  // counted by the select kernel: after the searches queued so far
@@ -2963,6 +2979,127 @@ int32_t vdb_index_search_recommend(vdb_index* ix, int32_t B, int32_t k, const in
     }
     ix->n_rec_searches++;
     ix->n_rec_queries += B;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_fused(vdb_index* ix, const float* queries, int32_t n_sub, const int64_t* set_offsets,
+                               int32_t n_sets, const double* weights, int32_t k, int32_t fetch_k, int32_t fusion,
+                               double rrf_c, const uint32_t* row_mask, int32_t mem, float* out_scores,
+                               int64_t* out_indices, double* out_fused, int32_t* out_hits, int64_t index_offset,
+                               void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    // everything checked before any launch (a device-memory call's offsets and weights: by the kernel)
+    switch (fuse_validate(n_sub, n_sets, k, fetch_k, fusion, rrf_c, queries != nullptr, set_offsets != nullptr,
+                          weights != nullptr, out_scores != nullptr, out_indices != nullptr, mem)) {
+        case kFuseBadCounts:
+            return set_error(VDB_ERR_INVALID, "n_sub and n_sets must be >= 0, got %d and %d", n_sub, n_sets);
+        case kFuseBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", kFuseMaxK, k);
+        case kFuseBadFetch:
+            return set_error(VDB_ERR_INVALID, "fetch_k must be in [k, %d], got fetch_k=%d k=%d", kFuseMaxFetch, fetch_k, k);
+        case kFuseBadFusion: return set_error(VDB_ERR_INVALID, "fusion must be VDB_FUSE_RRF or VDB_FUSE_MAX, got %d", fusion);
+        case kFuseBadC: return set_error(VDB_ERR_INVALID, "rrf_c must be finite and >= 0, got %g", rrf_c);
+        case kFuseNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/offset/output pointer");
+        case kFuseBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+        case kFuseWeightsWithMax: return set_error(VDB_ERR_INVALID, "weights must be NULL for VDB_FUSE_MAX");
+        default: break;
+    }
+    if (n_sets == 0) return VDB_OK;
+    const int D = ix->dim;
+    const bool host = mem == VDB_MEM_HOST;
+    if (host) {
+        int64_t at = 0;
+        switch (fuse_validate_lists(set_offsets, n_sets, n_sub, weights, &at)) {
+            case kFuseBadOffsets:
+                return set_error(VDB_ERR_INVALID, "set_offsets[%lld] = %lld: offsets must ascend from >= 0 to <= n_sub (%d)",
+                                 (long long)at, (long long)set_offsets[at], n_sub);
+            case kFuseSetTooLong:
+                return set_error(VDB_ERR_INVALID, "set %lld has more than %d sub-queries", (long long)at, kFuseMaxLists);
+            case kFuseBadWeight:
+                return set_error(VDB_ERR_INVALID, "weights[%lld] = %g: a weight must be finite and >= 0", (long long)at,
+                                 weights[at]);
+            default: break;
+        }
+        if (!all_finite(queries, (int64_t)n_sub * D)) return set_error(VDB_ERR_NONFINITE, "query contains NaN or Inf");
+    }
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // as vdb_index_search_mmr: the caller's stream, or for a host-memory call without one the
+    // stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const FuseScratch sc = fuse_scratch(n_sub, n_sets, D, k, fetch_k, N, host, weights != nullptr, masked,
+                                        out_fused != nullptr, out_hits != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    const float* Qd = queries;
+    const uint32_t* md = masked ? row_mask : nullptr;
+    FuseArgs a{};
+    a.offs = set_offsets; a.weights = weights;
+    a.out_s = out_scores; a.out_i = out_indices; a.out_f = out_fused; a.out_h = out_hits;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            if (n_sub > 0) std::memcpy(h + (sc.q - sc.in0), queries, (size_t)n_sub * D * 4);
+            std::memcpy(h + (sc.offs - sc.in0), set_offsets, ((size_t)n_sets + 1) * 8);
+            if (weights && n_sub > 0) std::memcpy(h + (sc.w - sc.in0), weights, (size_t)n_sub * 8);
+            if (masked) {
+                std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+                std::memset(h + (sc.mask - sc.in0) + sc.mask_words * 4, 0, 64 * 4);
+            }
+        });
+        if (rc) return rc;
+        Qd = reinterpret_cast<const float*>(dev + sc.q);
+        md = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.offs = reinterpret_cast<const int64_t*>(dev + sc.offs);
+        a.weights = weights ? reinterpret_cast<const double*>(dev + sc.w) : nullptr;
+        a.out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_f = out_fused ? reinterpret_cast<double*>(dev + sc.out_f) : nullptr;
+        a.out_h = out_hits ? reinterpret_cast<int32_t*>(dev + sc.out_h) : nullptr;
+    }
+    float* fs = reinterpret_cast<float*>(dev + sc.fs);
+    int64_t* fi = reinterpret_cast<int64_t*>(dev + sc.fi);
+    double* fk = reinterpret_cast<double*>(dev + sc.fk);
+    a.fs = fs; a.fi = fi; a.fk = fk;
+    a.k_fetch = fetch_k; a.k = k; a.n_sub = n_sub; a.rrf_c = rrf_c; a.count = N;
+    a.bad = ix->d_xmax + kFusedBadWord;
+    a.index_offset = index_offset;
+    const bool inner = N > 0 && n_sub > 0;
+    if (inner) {
+        // step 1: the lists, the best fetch_k eligible rows of every sub-query with their scores and
+        // keys, by the ordinary search in device memory on this stream (its own workspace,
+        // certificate and gated fallback; it counts the call in "searches" / "queries")
+        SearchOpts o;
+        rc = search_locked(ix, Qd, n_sub, fetch_k, md, VDB_MEM_DEVICE, fs, fi, fk, 0, st, nullptr, o);
+        if (rc == kRetryBf16x3) {
+            o.force_b3 = true;
+            rc = search_locked(ix, Qd, n_sub, fetch_k, md, VDB_MEM_DEVICE, fs, fi, fk, 0, st, nullptr, o);
+        }
+        if (rc) return rc;
+    }
+    // step 2: one workgroup per set (an empty index or a call without sub-queries: it reads no list
+    // and every slot is "no result"; a device-memory call's bad sets are still counted)
+    HIP_TRY(launch_fuse(fusion, a, n_sets, st));
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)n_sets * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)n_sets * k * 8);
+        if (out_fused) std::memcpy(out_fused, r + (sc.out_f - sc.out0), (size_t)n_sets * k * 8);
+        if (out_hits) std::memcpy(out_hits, r + (sc.out_h - sc.out0), (size_t)n_sets * k * 4);
+    }
+    if (!inner) {  // (otherwise the call was counted by its inner search)
+        ix->n_searches++;
+        ix->n_queries += n_sub;
+    }
+    ix->n_fused_searches++;
+    ix->n_fused_sets += n_sets;
     return VDB_OK;
 }
 

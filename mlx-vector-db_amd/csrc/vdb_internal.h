@@ -412,6 +412,19 @@ struct RecommendArgs {
 hipError_t launch_recommend_build(int metric, const RecommendArgs& a, int n_queries, hipStream_t st);
 hipError_t launch_recommend_select(int metric, const RecommendArgs& a, int n_queries, hipStream_t st);
 
+// Fused search (vdb_fuse.hip, vdb_index_search_fused).  fs / fi / fk [n_sub][k_fetch]: the lists of
+// all sub-queries (local rows, -1 = none, ranked by (key desc, row asc)), their fp32 scores and fp64
+// keys; offs [n_sets + 1] and weights (nullptr or [n_sub]) in device memory, read under the clamp and
+// the checks of vdb_fuse_plan.h whatever they hold (*bad += the sets found bad).  One workgroup per
+// set writes out_* [n_sets][k] (out_f / out_h optional).  count == 0 is allowed (no list is read).
+struct FuseArgs {
+    const float* fs; const int64_t* fi; const double* fk; int k_fetch; int k;
+    const int64_t* offs; int64_t n_sub; const double* weights; double rrf_c; int64_t count;
+    unsigned long long* bad;
+    float* out_s; int64_t* out_i; double* out_f; int32_t* out_h; int64_t index_offset;
+};
+hipError_t launch_fuse(int fusion, const FuseArgs& a, int n_sets, hipStream_t st);
+
 // Merge sorted fp64-key lists.  Element (q, j, e) lives at q*sq + j*sj + e, lists
 // have Lk entries; output [nq][KP] sorted.
 hipError_t launch_merge_f64_u32(int KP, const double* lk, const uint32_t* li, int n_lists, int Lk,

@@ -33,6 +33,8 @@ MEM_HOST = 0
 MEM_DEVICE = 1
 # largest beam (ef) vdb_graph_search accepts (csrc/vdb_graph.hip GS_EF_MAX)
 GRAPH_EF_MAX = 256
+# how vdb_index_search_fused combines a set's lists (include/vdb.h VDB_FUSE_*)
+FUSION_IDS = {"rrf": 0, "max": 1}
 
 # Every symbol include/vdb.h declares (tests/test_abi.py checks the .so exports them).
 EXPORTED_SYMBOLS = (
@@ -42,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
     "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
-    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -113,6 +115,8 @@ def load_library():
                                              c_vp, c_vp, c_i64, c_vp]),
             "vdb_index_search_recommend": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32,
                                                    c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+            "vdb_index_search_fused": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
+                                               ctypes.c_double, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -187,6 +191,27 @@ def rows_to_bitmap(mask_or_rows, count: int) -> np.ndarray:
     bits = np.zeros(max(need, 1) * 32, np.uint8)
     bits[rows] = 1
     return np.packbits(bits, bitorder="little").view(np.uint32)
+
+
+def pack_query_sets(sets, dim: int) -> Tuple[np.ndarray, np.ndarray]:
+    """A sequence of query sets, each [m, dim] (or one vector [dim]; m may be 0) -> what
+    vdb_index_search_fused takes: the sub-queries back to back, fp32 [n_sub, dim], and the int64
+    offsets [len(sets) + 1]."""
+    arrs = []
+    for a in sets:
+        a = np.asarray(a, dtype=np.float32)
+        if a.size == 0:
+            a = a.reshape(0, dim)
+        elif a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[1] != dim:
+            raise ValueError(f"a query set must have shape (m, {dim}), got {a.shape}")
+        arrs.append(a)
+    offs = np.zeros(len(arrs) + 1, np.int64)
+    if arrs:
+        np.cumsum([a.shape[0] for a in arrs], out=offs[1:])
+    q = np.concatenate(arrs) if arrs else np.zeros((0, dim), np.float32)
+    return np.ascontiguousarray(q, dtype=np.float32), offs
 
 
 def pack_row_lists(lists) -> Tuple[np.ndarray, np.ndarray]:
@@ -636,6 +661,71 @@ class NativeIndex:
             ctypes.c_void_p(out_scores_ptr or None), ctypes.c_void_p(out_idx_ptr or None),
             ctypes.c_void_p(out_keys_ptr or None), ctypes.c_void_p(out_queries_ptr or None), int(index_offset),
             ctypes.c_void_p(stream or None)))
+
+    # -- fused search --------------------------------------------------------------
+    def search_fused(self, queries: np.ndarray, set_offsets, k: int, fetch_k: int, fusion: str = "rrf", weights=None,
+                     rrf_c: float = 60.0, row_mask: Optional[np.ndarray] = None, with_fused: bool = False,
+                     with_hits: bool = False, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_fused, host memory: set s is the sub-queries
+        ``queries[set_offsets[s]:set_offsets[s + 1]]`` (``pack_query_sets`` builds the pair); each
+        sub-query's best ``fetch_k`` rows are fused per row, ``fusion="rrf"``: the sum over the lists
+        holding it of ``weights[l] / (rrf_c + rank)``, ``"max"``: its greatest key, and ranked by
+        (fused desc, row asc).  Returns (scores f32 [S,k], indices i64 [S,k][, fused f64 [S,k]][, hits
+        i32 [S,k]]); slots past min(k, candidates) are 0 / -1 / -inf / 0.  A set of more than 16
+        sub-queries, a bad weight or ``k`` / ``fetch_k`` outside 1 <= k <= fetch_k <= 200 raises
+        ValueError."""
+        if fusion not in FUSION_IDS:
+            raise ValueError(f"fusion must be one of {sorted(FUSION_IDS)}, got {fusion!r}")
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(-1, self.dim) if q.size == 0 else q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must have shape (n_sub, {self.dim}), got {np.shape(queries)}")
+        offs = np.ascontiguousarray(set_offsets, dtype=np.int64).reshape(-1)
+        if offs.size < 1:
+            raise ValueError("set_offsets needs n_sets + 1 entries")
+        n_sub, S = q.shape[0], offs.size - 1
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if w.size != n_sub:
+                raise ValueError(f"weights needs one entry per sub-query ({n_sub}), got {w.size}")
+        k = int(k)
+        scores = np.empty((S, max(k, 0)), dtype=np.float32)  # (a bad k is the library's to refuse)
+        idx = np.empty((S, max(k, 0)), dtype=np.int64)
+        fused = np.empty((S, max(k, 0)), dtype=np.float64) if with_fused else None
+        hits = np.empty((S, max(k, 0)), dtype=np.int32) if with_hits else None
+        mask_p = None
+        if row_mask is not None:
+            m = np.ascontiguousarray(row_mask, dtype=np.uint32)
+            need = (self.count() + 31) // 32
+            if m.size < need:
+                raise ValueError(f"row_mask needs {need} uint32 words, got {m.size}")
+            mask_p = _ptr(m)
+        _check(self._lib.vdb_index_search_fused(
+            self._h, _ptr(q) if n_sub else None, n_sub, _ptr(offs), S, _ptr(w) if w is not None and n_sub else None, k,
+            int(fetch_k), FUSION_IDS[fusion], float(rrf_c), mask_p, MEM_HOST, _ptr(scores), _ptr(idx),
+            _ptr(fused) if fused is not None else None, _ptr(hits) if hits is not None else None, int(index_offset), None))
+        out = (scores, idx)
+        if with_fused:
+            out += (fused,)
+        if with_hits:
+            out += (hits,)
+        return out
+
+    def search_fused_device(self, q_ptr: int, n_sub: int, set_offsets_ptr: int, n_sets: int, k: int, fetch_k: int,
+                            out_scores_ptr: int, out_idx_ptr: int, fusion: str = "rrf", weights_ptr: int = 0,
+                            rrf_c: float = 60.0, out_fused_ptr: int = 0, out_hits_ptr: int = 0, mask_ptr: int = 0,
+                            index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_fused with device-memory arguments (fp32 queries, int64 offsets, fp64
+        weights); stream-ordered, the offsets and weights are not validated on the host and nothing is
+        read back (a bad set comes back empty and counts in stat ``fused_bad_sets``)."""
+        _check(self._lib.vdb_index_search_fused(
+            self._h, ctypes.c_void_p(q_ptr or None), int(n_sub), ctypes.c_void_p(set_offsets_ptr or None), int(n_sets),
+            ctypes.c_void_p(weights_ptr or None), int(k), int(fetch_k), FUSION_IDS[fusion], float(rrf_c),
+            ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, ctypes.c_void_p(out_scores_ptr or None),
+            ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_fused_ptr or None),
+            ctypes.c_void_p(out_hits_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
 
 
 class NativeShards:

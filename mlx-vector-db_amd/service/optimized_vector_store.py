@@ -57,6 +57,12 @@ MMR_MAX_FETCH = 200
 # value outside them with 400
 REC_MAX_K = 136
 REC_MAX_EXAMPLES = 64
+# fused_query: the most rows per set, the most rows fetched per vector and the most vectors per set
+# (include/vdb.h vdb_index_search_fused); POST /vectors/fused_query answers a value outside them with
+# 400
+FUSED_MAX_K = 200
+FUSED_MAX_FETCH = 200
+FUSED_MAX_LISTS = 16
 
 
 # half the smallest measured crossover of the row-list search against the masked
@@ -973,6 +979,98 @@ class MLXVectorStore:
                 ib = idx[b][valid].tolist()
                 out.append((ib, scores[b][valid].astype(np.float64).tolist(),
                             [meta[i] if i < len(meta) else {} for i in ib]))
+            return out
+
+    # ---- fused query -------------------------------------------------------------------
+    def fused_query(self, query_vectors: Union[np.ndarray, Any], k: int = 10, fusion: str = "rrf", weights=None,
+                    fetch_k: Optional[int] = None, rrf_c: float = 60.0,
+                    filter_metadata: Optional[Dict] = None) -> Tuple:
+        """One ranked list from several query vectors ([m, dim], m <= 16: paraphrases of a question,
+        the question plus a hypothetical answer, a title and a body embedding) -> (indices, scores,
+        metadata, fused, hits), best first: as ``mmr_query``'s tuple, then each row's fused value
+        (fp64) and the number of the m lists that held it.  Each vector's best ``fetch_k`` rows
+        (``None``: min(200, max(k, 4 k))) are fused per row: ``fusion="rrf"`` adds ``weights[l] /
+        (rrf_c + rank)`` over the lists holding the row in list order (``weights`` None: all 1.0);
+        ``"max"`` takes its greatest exact key ("the best match to any of the vectors", exact over
+        the whole corpus; no weights).  Ties go to the lower row id.  Exact and the same for every
+        precision (include/vdb.h vdb_index_search_fused).  The reference has no such read."""
+        q = _as_matrix(query_vectors)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError(f"fused_query takes one set of vectors of shape (m, dim), got {q.shape}; "
+                             "use batch_fused_query for several sets")
+        return self.batch_fused_query([q], k, fusion, None if weights is None else [weights], fetch_k, rrf_c,
+                                      filter_metadata)[0]
+
+    def batch_fused_query(self, query_sets, k: int = 10, fusion: str = "rrf", weights=None,
+                          fetch_k: Optional[int] = None, rrf_c: float = 60.0,
+                          filter_metadata: Optional[Dict] = None) -> List[Tuple]:
+        """``fused_query`` for a list of query sets from one device call: one (indices, scores,
+        metadata, fused, hits) tuple per set.  ``weights``: None, or one sequence per set."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("fused query is not supported on a multi-device store")
+        k = int(k)
+        if not 1 <= k <= FUSED_MAX_K:
+            raise ValueError(f"k must be in [1, {FUSED_MAX_K}], got {k}")
+        fetch_k = min(FUSED_MAX_FETCH, max(k, 4 * k)) if fetch_k is None else int(fetch_k)
+        if not k <= fetch_k <= FUSED_MAX_FETCH:
+            raise ValueError(f"fetch_k must be in [k, {FUSED_MAX_FETCH}], got fetch_k={fetch_k} k={k}")
+        if fusion not in _vdb.FUSION_IDS:
+            raise ValueError(f"fusion must be one of {sorted(_vdb.FUSION_IDS)}, got {fusion!r}")
+        c = float(rrf_c)
+        if fusion == "rrf" and not 0.0 <= c < float("inf"):  # (a NaN fails both comparisons)
+            raise ValueError(f"rrf_c must be finite and >= 0, got {rrf_c}")
+        sets = []
+        for s in query_sets:
+            a = _as_matrix(s)
+            if a.size == 0:  # a set without a vector: no error, no result
+                a = np.zeros((0, 0), np.float32)
+            elif a.ndim == 1:
+                a = a[None, :]
+            if a.ndim != 2:
+                raise ValueError(f"a query set must be 2-D (m, dim), got {a.shape}")
+            if a.shape[0] > FUSED_MAX_LISTS:
+                raise ValueError(f"a query set takes at most {FUSED_MAX_LISTS} vectors, got {a.shape[0]}")
+            sets.append(a)
+        B = len(sets)
+        w = None
+        if weights is not None:
+            if fusion == "max":
+                raise ValueError("weights are not used with fusion='max'")
+            weights = list(weights)
+            if len(weights) != B:
+                raise ValueError(f"weights needs one sequence per query set ({B}), got {len(weights)}")
+            ws = [np.asarray(x, dtype=np.float64).reshape(-1) for x in weights]
+            for a, x in zip(sets, ws):
+                if x.size != a.shape[0]:
+                    raise ValueError(f"a set of {a.shape[0]} vectors needs {a.shape[0]} weights, got {x.size}")
+                if not (np.isfinite(x).all() and (x >= 0).all()):
+                    raise ValueError("weights must be finite and >= 0")
+            w = np.concatenate(ws) if ws else np.zeros(0, np.float64)
+        empty = [([], [], [], [], []) for _ in range(B)]
+        with _Read(self._rw):
+            # (never the graph path, never the coalescer: one exact device call for all sets)
+            if self._vector_count == 0 or B == 0:
+                return empty
+            dim = self._dim
+            for a in sets:
+                if a.shape[0] and a.shape[1] != dim:
+                    raise ValueError(f"Dimension mismatch: query has {a.shape[1]} dims, store holds {dim}")
+            Q, offs = _vdb.pack_query_sets(sets, dim)
+            mask = self._range_mask(Q, filter_metadata)  # None: no filter; False: nothing to search
+            if mask is False:
+                return empty
+            scores, idx, fused, hits = self._index.search_fused(Q, offs, k, fetch_k, fusion, w, c, row_mask=mask,
+                                                                with_fused=True, with_hits=True)
+            meta = self._metadata
+            out = []
+            for b in range(B):
+                valid = idx[b] >= 0
+                ib = idx[b][valid].tolist()
+                out.append((ib, scores[b][valid].astype(np.float64).tolist(),
+                            [meta[i] if i < len(meta) else {} for i in ib], fused[b][valid].tolist(),
+                            hits[b][valid].tolist()))
             return out
 
     # ---- recommend --------------------------------------------------------------------
