@@ -619,7 +619,8 @@ typedef struct vdb_graph vdb_graph;
 
 int32_t vdb_graph_build(vdb_index* idx, int32_t degree, int32_t knn, int32_t n_entries, vdb_graph** out);
 /* Persistence: a graph exported by vdb_graph_export (neighbours [n][degree], -1 =
- * none; entry rows) re-attached to an index holding the same rows. */
+ * none; entry rows) re-attached to an index holding the same rows.  The entry rows must be
+ * distinct: a repeated entry row is refused (VDB_ERR_INVALID), as is any id out of range. */
 int32_t vdb_graph_import(vdb_index* idx, int32_t degree, int64_t n, const int32_t* nbr, int32_t n_entries,
                          const int32_t* entries, vdb_graph** out);
 int32_t vdb_graph_export(const vdb_graph* g, int32_t* nbr_host, int32_t* entries_host);

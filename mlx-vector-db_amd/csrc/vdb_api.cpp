@@ -3530,6 +3530,12 @@ int32_t vdb_graph_import(vdb_index* ix, int32_t degree, int64_t n, const int32_t
         if (nbr[i] < -1 || nbr[i] >= n) return set_error(VDB_ERR_INVALID, "neighbour id out of range at %lld", (long long)i);
     for (int i = 0; i < n_entries; ++i)
         if (entries[i] < 0 || entries[i] >= n) return set_error(VDB_ERR_INVALID, "entry id out of range");
+    // The search kernel ranks the entries by counting the better ones: a repeated row would share
+    // its rank with its copy and leave a beam slot that is counted but never written.
+    std::vector<int32_t> sorted_ent(entries, entries + n_entries);
+    std::sort(sorted_ent.begin(), sorted_ent.end());
+    const auto rep = std::adjacent_find(sorted_ent.begin(), sorted_ent.end());
+    if (rep != sorted_ent.end()) return set_error(VDB_ERR_INVALID, "entry row %d is repeated", (int)*rep);
     HIP_TRY(hipSetDevice(ix->device));
     return graph_upload(ix, degree, n, nbr, entries, n_entries, out);
 }

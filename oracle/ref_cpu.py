@@ -519,3 +519,245 @@ def graph_build(X: np.ndarray, metric: str = "cosine", degree: int = 32, knn: in
     E = min(n_entries, max(N, 1))
     ent = np.asarray([i * N // E for i in range(E)], np.int32)
     return nbr, ent, amb
+
+
+# ---------------------------------------------------------------------------------
+# The graph path as the device runs it (vdb_graph.hip graph_search_kernel +
+# graph_merge_kernel; vdb_api.cpp vdb_graph_add), restated step for step.  Unlike
+# graph_search above (hnswlib's one-at-a-time form, a recall yardstick) these are
+# pins: on integer-valued rows with queries whose every fp32 product and sum is exact
+# they reproduce labels, distances, both statistics and every neighbour list bit for
+# bit (tests/test_gpu_graph_exact.py; the data conditions are checked on the CPU by
+# tests/test_graph_precondition.py).
+# ---------------------------------------------------------------------------------
+GS_WAVES = 4         # beam nodes expanded per iteration
+GS_ENT_MAX = 256     # entries every team scores; more are sliced per team
+GS_MAX_ITERS = 8192  # the kernel's hard stop
+GS_VIS = 16384       # visited hash slots
+GS_PROBE = 64        # linear probes before a row is treated as visited
+
+# Deliberately wrong variants of graph_beam_search / graph_add (`flaw=`), for the
+# teeth checks of tests/test_graph_precondition.py only: the case matrix must tell
+# each of them from the restatement.
+BEAM_FLAWS = ("one_expansion", "last_slot_ignored", "ties_to_higher_row", "entries_past_ef_unvisited",
+              "enter_without_room_clause", "dims_from_384_dropped", "contiguous_team_slices")
+# Not a flaw: testing a fresh row against the beam as the rows before it update it admits fewer
+# rows, but never drops one of the best ef of beam + fresh, so the merged beam is the same.  The
+# enter test is a filter ahead of an exact top-ef merge: only one that is too strict can show.
+BEAM_EQUIVALENT = ("enter_against_updated_beam",)
+ADD_FLAWS = ("no_sort", "in_edges_first")
+
+
+def graph_query_scores(vectors: np.ndarray, query: np.ndarray, metric: str, scales: np.ndarray | None = None,
+                       dims: int | None = None):
+    """wave_score_rows for every row: (fp32 scores [N], higher = better; fp32 |q|^2; the fp64
+    dot products the scores were rounded from).  Cosine: q_hat = q * (1 / max(sqrt(|q|^2), 1e-8))
+    in fp32, s = fl32(fl32(q_hat . x) * inv32[row]); L2: s = fl32(2 q . x - sq32[row]).  The dot
+    product is taken in fp64 and rounded once: the kernel's fp32 FMA chain gives the same bits
+    exactly when every partial sum is representable (the pin's data condition).  `vectors` may
+    be passed as fp64 (no copy); `dims` keeps only the leading dimensions (a teeth variant)."""
+    V = np.asarray(vectors, np.float64)
+    q = np.asarray(query, np.float32).reshape(-1)
+    if scales is None:
+        scales = _row_scales(V.astype(np.float32), metric)
+    q64 = q.astype(np.float64)
+    qn2 = np.float32(q64 @ q64)
+    if metric == "cosine":
+        inv = np.float32(1.0) / np.maximum(np.sqrt(qn2), np.float32(EPS))
+        qh = (q * inv).astype(np.float32)
+    else:
+        qh = q
+    d = V.shape[1] if dims is None else min(dims, V.shape[1])
+    dots = V[:, :d] @ qh[:d].astype(np.float64)
+    d32 = dots.astype(np.float32)
+    if metric == "cosine":
+        s = (d32 * scales.astype(np.float32)).astype(np.float32)
+    else:
+        s = (2.0 * d32.astype(np.float64) - scales.astype(np.float64)).astype(np.float32)
+    return s, qn2, dots
+
+
+def _beam_team(sl, lists, entries, n_rows, ef, T, team, flaw, trace):
+    """One workgroup of graph_search_kernel: (beam rows best first, iterations, rows scored)."""
+    sign = -1 if flaw == "ties_to_higher_row" else 1
+
+    def key(r):  # `better`: score descending, row ascending
+        return (-sl[r], sign * r)
+
+    nE = len(entries)
+    if nE <= GS_ENT_MAX:
+        order = sorted((int(r) for r in entries), key=key)
+        if flaw == "contiguous_team_slices":
+            per = -(-nE // T)
+            mine = order[team * per:(team + 1) * per]
+        else:
+            mine = order[team::T]  # ranks = team (mod T); beam position rank // T
+        scored = nE
+    else:
+        E = min(GS_ENT_MAX, -(-nE // T))
+        step = max(1, nE // (T * E))
+        Ev = min(E, (nE // step - team + T - 1) // T)
+        mine = sorted((int(entries[(e * T + team) * step]) for e in range(Ev)), key=key)
+        scored = Ev
+    visited = set(mine[:ef] if flaw == "entries_past_ef_unvisited" else mine)
+    beam = mine[:ef]
+    expanded = [False] * len(beam)
+    width = 1 if flaw == "one_expansion" else GS_WAVES
+    iters = 0
+    if trace is not None and len(mine) > ef:
+        trace["entries_exceed_ef"] = trace.get("entries_exceed_ef", 0) + 1
+    while True:
+        picks = [i for i, x in enumerate(expanded) if not x][:width]
+        if not picks:
+            break
+        iters += 1
+        if iters > GS_MAX_ITERS:
+            break
+        bn = len(beam)
+        worst = key(beam[-1])  # the beam's last entry as of the start of the iteration
+        fresh = []
+        owner = {}
+        for i in picks:
+            expanded[i] = True
+            lst = lists[beam[i]]
+            if flaw == "last_slot_ignored":
+                lst = lst[:-1]
+            for nb in lst:
+                if nb < 0 or nb >= n_rows:
+                    continue
+                if nb in visited:
+                    if trace is not None and owner.get(nb, i) != i:
+                        trace["shared_neighbour"] = trace.get("shared_neighbour", 0) + 1
+                    continue
+                visited.add(nb)
+                owner[nb] = i
+                fresh.append(nb)
+        scored += len(fresh)
+        if flaw == "enter_against_updated_beam":
+            enter, last = [], worst
+            for r in fresh:
+                if bn + len(enter) < ef or key(r) < last:
+                    enter.append(r)
+                    last = max(last, key(r)) if bn + len(enter) <= ef else sorted([key(x) for x in beam + enter])[ef - 1]
+        elif flaw == "enter_without_room_clause":
+            enter = [r for r in fresh if key(r) < worst]
+        else:
+            enter = [r for r in fresh if bn < ef or key(r) < worst]
+        if trace is not None and bn + len(enter) > ef:
+            trace["beam_overflow"] = trace.get("beam_overflow", 0) + 1
+        merged = sorted(zip(beam + enter, expanded + [False] * len(enter)), key=lambda t: key(t[0]))[:ef]
+        beam = [r for r, _ in merged]
+        expanded = [x for _, x in merged]
+    if trace is not None:
+        trace.setdefault("visited_sets", []).append(visited)
+    return beam, iters, scored
+
+
+def graph_beam_search(vectors: np.ndarray, nbr: np.ndarray, entries: np.ndarray, query: np.ndarray, k: int, ef: int,
+                      metric: str = "cosine", teams: int = 1, scales: np.ndarray | None = None,
+                      n_rows: int | None = None, flaw: str | None = None, trace: dict | None = None):
+    """graph_search_kernel + graph_merge_kernel for one query, as the code does it.
+
+    Per team t of T = min(teams, max(n_entries, 1)).  Up to 256 entries: all are scored and
+    ranked by (score desc, row asc); the team takes the ranks = t (mod T) at beam position
+    rank // T, positions < ef enter the beam, every entry of the team is marked visited, and
+    `scored` starts at n_entries.  More entries: E = min(256, ceil(n / T)) slots, step =
+    max(1, n // (T E)), slot e reads entries[(e T + t) step], Ev = min(E, (n // step - t + T - 1)
+    // T) of them valid, ranked among themselves; `scored` starts at Ev.  Loop: the first <= 4
+    unexpanded beam positions are expanded together (none: stop); their neighbour entries with
+    0 <= id < n_rows not yet visited are the fresh rows (marked visited, counted in `scored`);
+    a fresh row enters if the beam held fewer than ef rows or it is better than the beam's last
+    row, both as of the start of the iteration; the new beam is the best ef of beam + entering,
+    expanded flags carried over.  Output: the first k beam rows, distance fl32(1 - s) (cosine) /
+    max(fl32(|q|^2 - s), 0) (L2), -1 / inf padded; with T > 1 the teams' lists merged into the
+    first k distinct rows by (distance asc, row asc).
+
+    Returns (labels int64 [k], distances fp32 [k], iterations, rows scored), the last two summed
+    over the teams (vdb_graph_stat "iterations" / "visited").  The visited hash is modelled as an
+    exact set: the kernel's differs only where a probe chain reaches 64 slots, which callers
+    exclude (trace["visited_sets"] holds each team's set for that check).  `trace`, if given,
+    also counts shared_neighbour (a fresh row met again from another pick in the same iteration),
+    beam_overflow (beam + entering > ef) and entries_exceed_ef (teams)."""
+    if flaw is not None and flaw not in BEAM_FLAWS + BEAM_EQUIVALENT:
+        raise ValueError(flaw)
+    nbr = np.asarray(nbr)
+    n_rows = nbr.shape[0] if n_rows is None else n_rows
+    s, qn2, _ = graph_query_scores(vectors, query, metric, scales, 384 if flaw == "dims_from_384_dropped" else None)
+    sl = s.tolist()
+    lists = nbr.tolist()
+    ent = np.asarray(entries).reshape(-1)
+    T = min(int(teams), max(ent.size, 1))
+    rows, iters, scored = [], 0, 0
+    for t in range(T):
+        beam, it, sc = _beam_team(sl, lists, ent, n_rows, ef, T, t, flaw, trace)
+        rows.append(beam[:k])
+        iters += it
+        scored += sc
+    pairs = []
+    for beam in rows:
+        r = np.asarray(beam, np.int64)
+        sv = s[r]
+        if metric == "cosine":
+            d = (np.float32(1.0) - sv).astype(np.float32)
+        else:
+            d = np.maximum((qn2 - sv).astype(np.float32), np.float32(0.0))
+        pairs += list(zip(d.tolist(), beam))
+    if T > 1:  # graph_merge_kernel: distinct (distance, row) pairs, ascending
+        sign = -1 if flaw == "ties_to_higher_row" else 1
+        pairs = sorted(set(pairs), key=lambda p: (p[0], sign * p[1]))[:k]
+    labels = np.full(k, -1, np.int64)
+    dists = np.full(k, np.inf, np.float32)
+    for i, (dv, rv) in enumerate(pairs):
+        labels[i], dists[i] = rv, dv
+    return labels, dists, iters, scored
+
+
+def graph_add(X: np.ndarray, nbr: np.ndarray, n0: int, metric: str = "cosine", degree: int = 32, knn: int = 32,
+              fill: bool = False, flaw: str | None = None) -> np.ndarray:
+    """vdb_graph_add restated: the neighbour array [N, degree] after rows [n0, N) of X were
+    inserted into a graph whose array over rows [0, n0) was `nbr`.  kk = min(max(knn, F) + 1, N)
+    with F = max(1, degree // 2); exact kNN of the new rows over all rows; candidates = the kNN
+    with self and -1 dropped, first min(knn, 63); pass 1 = select_neighbors(limit F, unsorted,
+    no fill); in-edge lists in ascending order of the new row; affected = the new rows plus the
+    old rows that gain an in-edge; pool of an old row = its current list (skipping -1, itself
+    and repeats), of a new row = its pass-1 list, then the in-edges, capped at 63; pass 2 =
+    select_neighbors(limit degree, sort, fill).  Unaffected rows keep their lists."""
+    if flaw is not None and flaw not in ADD_FLAWS:
+        raise ValueError(flaw)
+    X = np.asarray(X, np.float32)
+    N, R = X.shape[0], int(degree)
+    F = max(1, R // 2)
+    knn = max(int(knn), F)
+    out = np.full((N, R), -1, np.int32)
+    out[:n0] = np.asarray(nbr, np.int32)[:n0]
+    if N == n0:
+        return out
+    kk = min(knn + 1, N)
+    scales = _row_scales(X, metric)
+    if N <= 4096:  # exact_search's small-corpus branch, with the row norms taken once for all queries
+        xn = canonical_norm64(X) if metric == "cosine" else None
+        kid = [exact_topk_from_keys(exact_keys(X[i], X, metric, xn), kk) for i in range(n0, N)]
+    else:
+        _, kid, _ = exact_search(X[n0:], X, kk, metric)
+    CW = min(knn, 63)
+    fwd = {}
+    inn = {}
+    for i in range(n0, N):
+        c = [int(v) for v in kid[i - n0] if v >= 0 and v != i][:CW]
+        sel, _, _ = select_neighbors(X, scales, i, c + [-1] * (CW - len(c)), F, metric)
+        fwd[i] = [int(v) for v in sel if v >= 0]
+        for w in fwd[i]:
+            inn.setdefault(w, []).append(i)
+    affected = list(range(n0, N)) + sorted(w for w in inn if w < n0)
+    for v in affected:
+        own = fwd[v] if v >= n0 else [int(u) for u in out[v]]
+        gained = inn.get(v, [])
+        pool = []
+        for u in (gained + own if flaw == "in_edges_first" else own + gained):
+            if u < 0 or u == v or len(pool) >= 63 or u in pool:
+                continue
+            pool.append(u)
+        sel, _, _ = select_neighbors(X, scales, v, pool + [-1] * (63 - len(pool)), R, metric, fill=fill,
+                                     sort=flaw != "no_sort")
+        out[v] = sel
+    return out

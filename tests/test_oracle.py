@@ -232,3 +232,78 @@ def test_l2_batch_chunked_equals_the_store_path():
             ri, rs, _ = ref_cpu.reference_store_search(Q[b], V, k, "euclidean")
             assert idx[b].tolist() == ri
             np.testing.assert_array_equal(dist[b], np.asarray(rs, np.float32))
+
+
+def _line(xs):
+    X = np.zeros((len(xs), 2), np.float32)
+    X[:, 0] = xs
+    return X
+
+
+def test_graph_beam_search_path_graph_by_hand():
+    """Rows at x = 0..7 linked to both neighbours, one entry (row 0), query at x = 6, ef 2: each
+    iteration expands the one unexpanded row and meets one fresh row, until row 6's expansion
+    meets row 7, which ties with the beam's last row 5 at distance 1 and loses to the lower id."""
+    X = _line(range(8))
+    nbr = np.asarray([[i - 1, i + 1 if i < 7 else -1] for i in range(8)], np.int32)
+    lab, dist, iters, scored = ref_cpu.graph_beam_search(X, nbr, [0], [6, 0], 2, 2, "euclidean")
+    assert lab.tolist() == [6, 5] and dist.tolist() == [0.0, 1.0]
+    assert (iters, scored) == (7, 8)
+    lab, dist, _, _ = ref_cpu.graph_beam_search(X, nbr, [0], [6, 0], 2, 2, "euclidean", flaw="ties_to_higher_row")
+    assert lab.tolist() == [6, 7]
+
+
+def test_graph_beam_search_star_by_hand():
+    """A centre (row 0) with five leaves, entered at leaf 3, ef 3.  Iteration 1 meets the centre,
+    iteration 2 its four other leaves (the beam had room, so all enter and the best 3 of 6 stay:
+    rows 1, 0, 2 at distances 0, 1, 1, the tie to the lower row), iteration 3 expands rows 1 and 2
+    together and meets nothing new.  The all-zero cosine query ties every row: order by row id."""
+    X = np.asarray([[0, 0], [1, 0], [2, 0], [0, 3], [-1, 0], [0, 1]], np.float32)
+    nbr = np.full((6, 5), -1, np.int32)
+    nbr[0] = [1, 2, 3, 4, 5]
+    nbr[1:, 0] = 0
+    trace = {}
+    lab, dist, iters, scored = ref_cpu.graph_beam_search(X, nbr, [3], [1, 0], 3, 3, "euclidean", trace=trace)
+    assert lab.tolist() == [1, 0, 2] and dist.tolist() == [0.0, 1.0, 1.0]
+    assert (iters, scored) == (3, 6) and trace["beam_overflow"] == 1
+    assert trace["visited_sets"] == [{0, 1, 2, 3, 4, 5}]
+    lab, dist, iters, scored = ref_cpu.graph_beam_search(X, nbr, [3], [0, 0], 3, 3, "cosine")
+    assert lab.tolist() == [0, 1, 2] and dist.tolist() == [1.0, 1.0, 1.0] and (iters, scored) == (3, 6)
+    # degree 1 (the first list slot only): 3 -> 0 -> 1 and no farther; unreachable slots are -1 / inf
+    lab, dist, _, _ = ref_cpu.graph_beam_search(X, nbr[:, :1], [3], [1, 0], 4, 4, "euclidean")
+    assert lab.tolist() == [1, 0, 3, -1] and dist.tolist() == [0.0, 1.0, 10.0, np.inf]
+
+
+def test_graph_beam_search_two_components_by_hand():
+    """Two pairs {0, 1} and {2, 3}, entries 0 and 2, two teams: both teams score both entries (2
+    each), team 0 takes the better entry (row 2) and team 1 row 0; each finds its pair's other row
+    in one more step.  The merge takes the distinct rows by (distance, row): rows 1 and 2 tie at 4."""
+    X = _line([0, 1, 5, 4])
+    nbr = np.asarray([[1], [0], [3], [2]], np.int32)
+    lab, dist, iters, scored = ref_cpu.graph_beam_search(X, nbr, [0, 2], [3, 0], 2, 2, "euclidean", teams=2)
+    assert lab.tolist() == [3, 1] and dist.tolist() == [1.0, 4.0]
+    assert (iters, scored) == (4, 6)
+    lab, dist, iters, scored = ref_cpu.graph_beam_search(X, nbr, [0, 2], [3, 0], 2, 2, "euclidean", teams=1)
+    assert lab.tolist() == [3, 1] and (iters, scored) == (2, 4)  # one team expands both pairs at once
+    lab, _, _, _ = ref_cpu.graph_beam_search(X, nbr, [0, 2], [3, 0], 2, 2, "euclidean", teams=7)  # clamped to 2
+    assert lab.tolist() == [3, 1]
+
+
+def test_graph_add_by_hand():
+    """Degree 2 (one out-edge per new row, F = 1).  Path: a row inserted at x = 11 links to row 1,
+    whose pool [0, 2, new] is visited nearest first and keeps [new, 0].  Star: the centre's pool
+    [1, 2, new] keeps the new row at (1, 0), drops row 1 behind it, keeps row 2.  Two components:
+    rows far from the old pair link to each other only and the old lists stay."""
+    X = _line([0, 10, 20, 11])
+    got = ref_cpu.graph_add(X, np.asarray([[1, -1], [0, 2], [1, -1]], np.int32), 3, "euclidean", degree=2, knn=2)
+    assert got.tolist() == [[1, -1], [3, 0], [1, -1], [1, -1]]
+    X = np.asarray([[0, 0], [4, 0], [0, 4], [1, 0]], np.float32)
+    old = np.asarray([[1, 2], [0, -1], [0, -1]], np.int32)
+    for fill in (False, True):
+        got = ref_cpu.graph_add(X, old, 3, "euclidean", degree=2, knn=2, fill=fill)
+        assert got.tolist() == [[3, 2], [0, -1], [0, -1], [0, -1]]
+    assert ref_cpu.graph_add(X, old, 3, "euclidean", degree=2, knn=2, flaw="no_sort")[0].tolist() == [1, 2]
+    X = _line([0, 1, 100, 101])
+    got = ref_cpu.graph_add(X, np.asarray([[1, -1], [0, -1]], np.int32), 2, "euclidean", degree=2, knn=2)
+    assert got.tolist() == [[1, -1], [0, -1], [3, -1], [2, -1]]
+    assert ref_cpu.graph_add(X[:2], got[:2], 2, "euclidean", degree=2, knn=2).tolist() == [[1, -1], [0, -1]]
