@@ -154,7 +154,8 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "group_sets", "group_searches", "group_queries", "group_fallback_queries" are described
  * there; vdb_index_search_mmr's are "mmr_searches", "mmr_queries"; vdb_index_search_recommend's
  * "recommend_searches", "recommend_queries", "recommend_bad_queries"; vdb_index_search_fused's
- * "fused_searches", "fused_sets", "fused_bad_sets").  Stats also: "searches", "queries",
+ * "fused_searches", "fused_sets", "fused_bad_sets"; vdb_index_search_maxsim's "maxsim_searches",
+ * "maxsim_sets", "maxsim_bad_sets", "maxsim_skipped_rows").  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -567,6 +568,72 @@ int32_t vdb_index_search_fused(vdb_index* idx, const float* queries, int32_t n_s
                                const uint32_t* row_mask, int32_t mem,
                                float* out_scores, int64_t* out_indices, double* out_fused, int32_t* out_hits,
                                int64_t index_offset, void* stream);
+
+/* --- MaxSim search: groups ranked by the summed best match per query vector ---------
+ * Replaces: nothing the reference has.  Multi-vector ("late interaction") retrieval -- ColBERT /
+ * ColPali token embeddings, Qdrant's multivector MAX_SIM, Vespa's and Milvus' MaxSim -- scores a
+ * document by  sum over the query's vectors t of  max over the document's rows r of sim(q_t, r).
+ * A document is a group of the column vdb_index_set_groups attached.  No other call gives this
+ * answer: vdb_index_search_groups ranks by one vector's best row, VDB_FUSE_MAX takes the maximum
+ * over vectors, and summing over-fetched per-vector lists on the host is wrong (a document that is
+ * second best for every vector stands in no list and can still have the best sum).
+ *
+ *   queries      [n_sub, dim] fp32: the sub-queries of all sets, back to back
+ *   set_offsets  [n_sets + 1] int64, CSR as vdb_index_search_fused's: set s is sub-queries
+ *                [set_offsets[s], set_offsets[s + 1]).  A set has 0..64 sub-queries; one without
+ *                any is no error, all its slots are "no result".
+ *   n_sub        host scalar: the launches are sized from it, so a device-memory call reads nothing
+ *                back
+ *   n_group_slots  host scalar: the caller states that the attached group ids lie in
+ *                [0, n_group_slots); the launches and the scratch are sized from it.  1 <=
+ *                n_group_slots and n_sub * n_group_slots <= 2^27 (a 1 GiB table).  A row whose id is
+ *                at or past it is treated as a row without a group and counted in stat
+ *                "maxsim_skipped_rows" (both memory kinds: the column lives on the device).
+ *   k            1..128
+ *   out_scores   [n_sets, k] fp32; out_groups [n_sets, k] int32; out_sums NULL or [n_sets, k] fp64
+ *   row_mask, mem, stream: as vdb_index_search_groups; all pointers of one memory kind.
+ *                n_sets == 0 is VDB_OK.
+ * Contract: a row r is eligible when 0 <= group[r] < n_group_slots and its mask bit is set.  For
+ * sub-query t and group g, m[t][g] = the maximum over g's eligible rows r of (key(q_t, r) + 0.0),
+ * key the canonical fp64 key vdb_index_search ranks by; the one fp64 add turns -0.0 (the euclidean
+ * key of an exact match) into +0.0, so equal values have equal bits and the maximum of a set of
+ * values is one bit pattern in whatever order it is formed.  sum[s][g]: acc = 0.0, then for t
+ * ascending within the set acc = acc + m[t][g], separate fp64 adds.  A group without an eligible row
+ * is no candidate (eligibility does not depend on t, so a candidate has all its maxima).  Ranking:
+ * candidates by (sum desc, group id asc); the first min(k, candidates) are written: out_groups = the
+ * id, out_sums = sum, out_scores = (float)sum (round to nearest even), in key units for both
+ * metrics (euclidean: minus the summed squared distances, as MMR's stay in key units).  Slots past
+ * that hold group -1 / score 0 / sum -inf.
+ * Consequences: a set of one sub-query gives, per group, the key vdb_index_search_groups returns
+ * for that group (+ 0.0), in the same order.  The result of a set depends only on its own
+ * sub-queries.  The result is the same bytes for every precision setting and both memory kinds: the
+ * rows come from the fp32 copy and the candidate copies are not read.
+ * How: a table T [n_sub][n_group_slots] of order-preserving uint64 encodings, zeroed per call; one
+ * scan of the rows per block of up to 64 sub-queries (the shape of the range scan) folds runs of
+ * rows of one group in registers and issues one 64-bit atomic maximum per (wave, sub-query, run);
+ * one rank kernel sums each set's entries in sub-query order and keeps the best k.  A maximum does
+ * not depend on arrival order; no sum is formed by an atomic.
+ * Errors, before anything is launched, both memory kinds: no group column attached, k outside [1,
+ * 128], n_group_slots < 1 or the table above 2^27 entries, n_sub or n_sets < 0, a NULL queries with
+ * n_sub > 0, a NULL set_offsets / out_scores / out_groups with n_sets > 0, a bad mem ->
+ * VDB_ERR_INVALID.  Host-memory calls also: offsets that decrease or pass n_sub, a set of more than
+ * 64 -> VDB_ERR_INVALID; a NaN or Inf in a query -> VDB_ERR_NONFINITE (no stat moves).
+ * Device-memory calls are stream-ordered and read nothing back, so the kernel handles bad input
+ * itself: offsets are clamped to [0, n_sub] and nothing out of bounds is read; a set whose offsets
+ * decrease or lie outside [0, n_sub] or that is longer than 64 is answered with all slots "no
+ * result" and counted on the device in stat "maxsim_bad_sets"; the other sets are unaffected.
+ * Takes the index's shared lock and a per-search workspace, as vdb_index_search_groups does.  An
+ * empty index with an empty column attached gives every slot "no result".  Stats (cumulative,
+ * successful calls): "maxsim_searches", "maxsim_sets", "maxsim_bad_sets", "maxsim_skipped_rows"
+ * (rows, masked or not, with an id at or past n_group_slots, counted while the call's first block of
+ * sub-queries is scanned: once per call that scans).  "searches" / "queries" and every "searches_*"
+ * stat stay still. */
+int32_t vdb_index_search_maxsim(vdb_index* idx, const float* queries, int32_t n_sub,
+                                const int64_t* set_offsets, int32_t n_sets,
+                                int32_t n_group_slots, int32_t k,
+                                const uint32_t* row_mask, int32_t mem,
+                                float* out_scores, int32_t* out_groups, double* out_sums,
+                                void* stream);
 
 /* --- multi-GPU merge -----------------------------------------------------------
  * Merge per-shard top-k lists (all device memory, already all-gathered):

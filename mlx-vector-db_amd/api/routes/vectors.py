@@ -97,6 +97,19 @@ class VectorFusedQuery(BaseModel):
     filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
 
 
+class VectorMaxSimQuery(BaseModel):
+    """Late-interaction ("MaxSim") retrieval: the ``k`` best values of the metadata key ``group_by``
+    (documents of a multi-vector corpus) for a set of query vectors (token embeddings).  A group's
+    score is the sum, over the query vectors, of the vector's best match among the group's rows.  The
+    store checks the limits (at most 64 vectors, k at most 128); a value outside them is a 400."""
+    user_id: str
+    model_id: str
+    queries: List[List[float]] = Field(..., description="The query vectors (e.g. one per query token)")
+    group_by: str = Field(..., description="Metadata key whose values are the groups (documents)")
+    k: int = Field(default=10, description="Groups returned")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+
+
 class VectorRecommendQuery(BaseModel):
     """Rows like the stored examples ``positive`` and unlike ``negative``: row indices, or with
     ``key`` (a metadata field, e.g. "doc_id") values of that field, every row holding one of them an
@@ -196,6 +209,14 @@ class VectorFusedQueryResponse(BaseModel):
     # "similarity_score" and "distance" of the best-matching vector
     results: List[Dict[str, Any]]
     fusion: str
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorMaxSimQueryResponse(BaseModel):
+    # best group first: {"group_value", "score" (the sum in the store's ranking-key units: cosine
+    # similarities, or minus the squared distances for euclidean), "rank"}
+    groups: List[Dict[str, Any]]
     query_time_ms: float
     total_vectors_searched: int
 
@@ -497,6 +518,34 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in fused query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Fused query failed: {e}")
+
+    @router.post("/maxsim_query", response_model=VectorMaxSimQueryResponse)
+    async def maxsim_query_vectors(request: VectorMaxSimQuery, api_key: str = Depends(auth)):
+        """The ``k`` best groups (distinct values of ``group_by``) by the summed best match of every
+        query vector, best first.  A bad request (no vector, more than 64, k outside its limits,
+        dimension mismatch: the store's ValueError) is a 400, an unsupported store a 501, anything
+        else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if not request.queries or not all(request.queries):
+                raise HTTPException(status_code=400, detail="Query vectors required")
+            loop = asyncio.get_running_loop()
+            groups = await loop.run_in_executor(
+                mgr._executor, lambda: store.maxsim_query(request.queries, request.group_by, k=request.k,
+                                                          filter_metadata=request.filter_metadata))
+            out = [{"group_value": g["group"], "score": g["sum"], "rank": i + 1} for i, g in enumerate(groups)]
+            return VectorMaxSimQueryResponse(groups=out, query_time_ms=(time.time() - t0) * 1000,
+                                             total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"MaxSim query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"MaxSim query failed: {e}")
+        except Exception as e:
+            logger.error("Error in MaxSim query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"MaxSim query failed: {e}")
 
     @router.post("/recommend", response_model=VectorQueryResponse)
     async def recommend_vectors(request: VectorRecommendQuery, api_key: str = Depends(auth)):

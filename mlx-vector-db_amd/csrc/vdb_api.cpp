@@ -29,6 +29,7 @@
 #include "vdb_group_plan.h"
 #include "vdb_mmr_plan.h"
 #include "vdb_fuse_plan.h"
+#include "vdb_maxsim_plan.h"
 #include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
 #include "vdb_internal.h"
@@ -63,6 +64,9 @@ constexpr size_t kGatedExactBytes = 256u << 20;  // device-gated fallback lists 
 constexpr int kSubsetBadWord = 12;        // d_xmax word (8 bytes each) counting a row-list search's skipped ids
 constexpr int kRecommendBadWord = 13;     // d_xmax word counting the queries a recommend search flagged on the device
 constexpr int kFusedBadWord = 14;         // d_xmax word counting the sets a fused search found bad on the device
+constexpr int kMaxsimBadWord = 24;        // d_xmax word counting the sets a MaxSim search found bad on the device
+constexpr int kMaxsimSkippedWord = 25;    // d_xmax word counting the rows MaxSim searches skipped for an id past the slots
+constexpr size_t kXmaxBytes = 256;        // d_xmax in all (layout: vdb_index_create)
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 inline int next_pow2(int v) {
@@ -261,6 +265,9 @@ struct vdb_index {
     // vdb_index_search_fused: calls and sets (successful calls); the sets its kernel found bad are
     // counted on the device (d_xmax + kFusedBadWord)
     std::atomic<int64_t> n_fused_searches{0}, n_fused_sets{0};
+    // vdb_index_search_maxsim: calls and sets (successful calls); the sets its rank kernel found bad
+    // and the rows its scan skipped are counted on the device (d_xmax + kMaxsimBadWord / SkippedWord)
+    std::atomic<int64_t> n_maxsim_searches{0}, n_maxsim_sets{0};
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -870,9 +877,11 @@ int32_t vdb_index_create(int32_t dim, int32_t metric, int32_t device, vdb_index*
     // [128, 192) an add's snapshot of the maxima and of d_i8 (restored when the add is rejected),
     // [96, 104) the ids row-list searches skipped (kSubsetBadWord; cumulative, a clear keeps it),
     // [104, 112) the queries recommend searches flagged (kRecommendBadWord; likewise),
-    // [112, 120) the sets fused searches found bad (kFusedBadWord; likewise)
-    if (e == hipSuccess) e = hipMalloc(&ix->d_xmax, 192);
-    if (e == hipSuccess) e = zero_now(ix->d_xmax, 192, ix->stream);
+    // [112, 120) the sets fused searches found bad (kFusedBadWord; likewise),
+    // [192, 200) the sets MaxSim searches found bad and [200, 208) the rows they skipped
+    // (kMaxsimBadWord, kMaxsimSkippedWord; likewise)
+    if (e == hipSuccess) e = hipMalloc(&ix->d_xmax, kXmaxBytes);
+    if (e == hipSuccess) e = zero_now(ix->d_xmax, kXmaxBytes, ix->stream);
     if (e == hipSuccess) e = hipMalloc(&ix->d_i8, 64);
     if (e == hipSuccess) e = zero_now(ix->d_i8, 64, ix->stream);
     if (e == hipSuccess) e = hipMalloc(&ix->d_csum, (size_t)2 * ix->Dp * sizeof(uint32_t));
@@ -1189,6 +1198,17 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
         unsigned long long bad = 0;
         HIP_TRY(hipMemcpy(&bad, ix->d_xmax + kFusedBadWord, sizeof(bad), hipMemcpyDeviceToHost));
         *value = (int64_t)bad;
+    }
+    else if (n == "maxsim_searches") *value = ix->n_maxsim_searches.load();
+    else if (n == "maxsim_sets") *value = ix->n_maxsim_sets.load();
+    else if (n == "maxsim_bad_sets" || n == "maxsim_skipped_rows") {  // counted by the kernels: after the searches queued so far
+        HIP_TRY(hipSetDevice(ix->device));
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+        unsigned long long c = 0;
+        HIP_TRY(hipMemcpy(&c, ix->d_xmax + (n == "maxsim_bad_sets" ? kMaxsimBadWord : kMaxsimSkippedWord), sizeof(c),
+                          hipMemcpyDeviceToHost));
+        *value = (int64_t)c;
     }
     else if (n == "group_fallback_queries") {  // counted by the select kernel: after the searches queued so far
         unsigned long long fb = 0;
@@ -3100,6 +3120,118 @@ int32_t vdb_index_search_fused(vdb_index* ix, const float* queries, int32_t n_su
     }
     ix->n_fused_searches++;
     ix->n_fused_sets += n_sets;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_maxsim(vdb_index* ix, const float* queries, int32_t n_sub, const int64_t* set_offsets,
+                                int32_t n_sets, int32_t n_group_slots, int32_t k, const uint32_t* row_mask, int32_t mem,
+                                float* out_scores, int32_t* out_groups, double* out_sums, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    // everything checked before any launch (a device-memory call's offsets: by the rank kernel; the
+    // column itself under the lock, below)
+    switch (maxsim_validate(n_sub, n_sets, n_group_slots, k, queries != nullptr, set_offsets != nullptr,
+                            out_scores != nullptr, out_groups != nullptr, mem)) {
+        case kMaxsimBadCounts:
+            return set_error(VDB_ERR_INVALID, "n_sub and n_sets must be >= 0, got %d and %d", n_sub, n_sets);
+        case kMaxsimBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", kMaxsimMaxK, k);
+        case kMaxsimBadSlots:
+            return set_error(VDB_ERR_INVALID,
+                             "n_group_slots must be >= 1 and n_sub * n_group_slots <= %lld, got %d slots for %d sub-queries",
+                             (long long)kMaxsimMaxCells, n_group_slots, n_sub);
+        case kMaxsimNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/offset/output pointer");
+        case kMaxsimBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+        default: break;
+    }
+    if (n_sets == 0) return VDB_OK;
+    const int D = ix->dim;
+    const bool host = mem == VDB_MEM_HOST;
+    if (host) {
+        int64_t at = 0;
+        switch (maxsim_validate_sets(set_offsets, n_sets, n_sub, &at)) {
+            case kMaxsimBadOffsets:
+                return set_error(VDB_ERR_INVALID, "set_offsets[%lld] = %lld: offsets must ascend from >= 0 to <= n_sub (%d)",
+                                 (long long)at, (long long)set_offsets[at], n_sub);
+            case kMaxsimSetTooLong:
+                return set_error(VDB_ERR_INVALID, "set %lld has more than %d sub-queries", (long long)at, kMaxsimMaxVectors);
+            default: break;
+        }
+        if (!all_finite(queries, (int64_t)n_sub * D)) return set_error(VDB_ERR_NONFINITE, "query contains NaN or Inf");
+    }
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    if (!ix->group_set || ix->group_n != N)
+        return set_error(VDB_ERR_INVALID, "no group column is attached (vdb_index_set_groups; add, remove and clear drop it)");
+    // as vdb_index_search_groups: the caller's stream (device memory: NULL = the null stream), or for
+    // a host-memory call without one the stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const bool scan = N > 0 && n_sub > 0;
+    const MaxsimScratch sc = maxsim_scratch(n_sub, n_sets, scan ? n_group_slots : 1, D, range_query_block(ix->Dp), k, N,
+                                            host, masked, out_sums != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    MaxsimScanArgs a{};
+    MaxsimRankArgs ra{};
+    a.Q = queries;
+    a.mask = masked ? row_mask : nullptr;
+    ra.offs = set_offsets;
+    ra.out_s = out_scores; ra.out_g = out_groups; ra.out_sum = out_sums;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            if (n_sub > 0) std::memcpy(h + (sc.q - sc.in0), queries, (size_t)n_sub * D * 4);
+            std::memcpy(h + (sc.offs - sc.in0), set_offsets, ((size_t)n_sets + 1) * 8);
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+        });
+        if (rc) return rc;
+        a.Q = reinterpret_cast<const float*>(dev + sc.q);
+        a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        ra.offs = reinterpret_cast<const int64_t*>(dev + sc.offs);
+        ra.out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        ra.out_g = reinterpret_cast<int32_t*>(dev + sc.out_g);
+        ra.out_sum = out_sums ? reinterpret_cast<double*>(dev + sc.out_sum) : nullptr;
+    }
+    unsigned long long* T = reinterpret_cast<unsigned long long*>(dev + sc.T);
+    // the table and the rank kernel's per-set counters, zeroed together
+    HIP_TRY(hipMemsetAsync(T, 0, (size_t)sc.zero_bytes, st));
+    if (scan) {
+        double* qn64 = reinterpret_cast<double*>(dev + sc.qn64);
+        // the canonical query norms, nothing else: no query tiles
+        HIP_TRY(launch_prep_queries(a.Q, n_sub, n_sub, D, ix->G, ix->metric, nullptr, nullptr, qn64, nullptr, nullptr,
+                                    nullptr, nullptr, nullptr, st));
+        a.qn64 = qn64;
+        a.X = ix->X; a.G = ix->G; a.D = D; a.nrm64 = ix->nrm64; a.N = N;
+        a.groups = ix->groups; a.n_slots = n_group_slots; a.T = T;
+        // block after block on this stream into the one table; the first counts the rows it skips
+        for (int b0 = 0; b0 < n_sub; b0 += sc.block) {
+            a.skipped = b0 == 0 ? ix->d_xmax + kMaxsimSkippedWord : nullptr;
+            HIP_TRY(launch_maxsim_scan(ix->metric, a, b0, std::min(sc.block, n_sub - b0), st));
+        }
+    }
+    // one rank launch for all sets (an empty index or a call without sub-queries: it reads no table
+    // and every slot is "no result"; a device-memory call's bad sets are still counted)
+    ra.T = T; ra.n_slots = scan ? n_group_slots : 1; ra.scanned = scan ? 1 : 0;
+    ra.n_sub = n_sub; ra.k = k; ra.KE = sc.KE;
+    ra.lk = reinterpret_cast<double*>(dev + sc.lk); ra.li = reinterpret_cast<uint32_t*>(dev + sc.li);
+    ra.mk = reinterpret_cast<double*>(dev + sc.mk); ra.mi = reinterpret_cast<uint32_t*>(dev + sc.mi);
+    ra.done = reinterpret_cast<int*>(dev + sc.done);
+    ra.bad = ix->d_xmax + kMaxsimBadWord;
+    HIP_TRY(launch_maxsim_rank(ra, n_sets, sc.n_seg, st));
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)n_sets * k * 4);
+        std::memcpy(out_groups, r + (sc.out_g - sc.out0), (size_t)n_sets * k * 4);
+        if (out_sums) std::memcpy(out_sums, r + (sc.out_sum - sc.out0), (size_t)n_sets * k * 8);
+    }
+    ix->n_maxsim_searches++;
+    ix->n_maxsim_sets += n_sets;
     return VDB_OK;
 }
 

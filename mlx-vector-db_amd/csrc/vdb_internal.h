@@ -425,6 +425,36 @@ struct FuseArgs {
 };
 hipError_t launch_fuse(int fusion, const FuseArgs& a, int n_sets, hipStream_t st);
 
+// MaxSim search (vdb_maxsim.hip, vdb_index_search_maxsim).  Scan: sub-queries [b0, b0 + qb) of the
+// call (qb at most kRangeMaxBlock, vdb_range_plan.h) against rows [0, N), N >= 1.  A row is eligible
+// when its group id lies in [0, n_slots) and mask (optional, the row_mask layout) has its bit;
+// T [n_sub][n_slots] (zero on entry) gets, by 64-bit atomic maximum, the entry (vdb_maxsim_plan.h
+// maxsim_entry) of the greatest canonical fp64 key of each (sub-query, slot) over the eligible rows.
+// skipped (optional; the call's first block passes it): *skipped += the rows, masked or not, whose
+// id is at or past n_slots.  groups holds at least N ids.
+struct MaxsimScanArgs {
+    const float* Q; const double* qn64; const float* X; int G; int D; const double* nrm64; int64_t N;
+    const uint32_t* mask; const int32_t* groups; int32_t n_slots;
+    unsigned long long* T; unsigned long long* skipped;
+};
+hipError_t launch_maxsim_scan(int metric, const MaxsimScanArgs& a, int b0, int qb, hipStream_t st);
+// Rank: offs [n_sets + 1] in device memory, read under the clamp of vdb_maxsim_plan.h whatever it
+// holds (*bad += the sets found bad).  Set s: the slots whose entry for its first sub-query is not
+// 0, by (sum of the set's decoded entries in sub-query order desc, slot asc), the first k to out_*
+// [s][k] (out_sum optional), "no result" behind them.  Grid (n_seg, n_sets); with n_seg > 1 the
+// workgroup that finishes a set last merges the segments' lists lk / li [n_sets][n_seg][KE] through
+// mk / mi [n_sets][KE] (done [n_sets]: zero on entry, zero again on exit).  scanned == 0: T is not
+// read and no set has a candidate (an empty index, a call without sub-queries).
+struct MaxsimRankArgs {
+    const unsigned long long* T; int32_t n_slots; int scanned;
+    const int64_t* offs; int64_t n_sub; int k; int KE;
+    double* lk; uint32_t* li; double* mk; uint32_t* mi; int* done;
+    unsigned long long* bad;
+    float* out_s; int32_t* out_g; double* out_sum;
+};
+size_t maxsim_rank_lds_bytes(int KE, int n_seg);
+hipError_t launch_maxsim_rank(const MaxsimRankArgs& a, int n_sets, int n_seg, hipStream_t st);
+
 // Merge sorted fp64-key lists.  Element (q, j, e) lives at q*sq + j*sj + e, lists
 // have Lk entries; output [nq][KP] sorted.
 hipError_t launch_merge_f64_u32(int KP, const double* lk, const uint32_t* li, int n_lists, int Lk,

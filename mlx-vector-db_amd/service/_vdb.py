@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
     "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
-    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -117,6 +117,8 @@ def load_library():
                                                    c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_index_search_fused": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
                                                ctypes.c_double, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+            "vdb_index_search_maxsim": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp,
+                                                c_vp, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -726,6 +728,63 @@ class NativeIndex:
             ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, ctypes.c_void_p(out_scores_ptr or None),
             ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_fused_ptr or None),
             ctypes.c_void_p(out_hits_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
+
+    # -- MaxSim search -------------------------------------------------------------
+    def _maxsim_sets(self, query_sets):
+        """``query_sets``: a sequence of sets, each [m, dim] (``pack_query_sets``), or the packed
+        pair as a tuple ``(Q [n_sub, dim], offsets [n_sets + 1])`` -> (Q fp32, offsets int64)."""
+        if isinstance(query_sets, tuple) and len(query_sets) == 2:
+            o = np.asarray(query_sets[1])
+            if o.ndim == 1 and o.dtype.kind in "iu":
+                q = np.ascontiguousarray(query_sets[0], dtype=np.float32)
+                if q.ndim == 1:
+                    q = q.reshape(-1, self.dim) if q.size == 0 else q[None, :]
+                if q.ndim != 2 or q.shape[1] != self.dim:
+                    raise ValueError(f"queries must have shape (n_sub, {self.dim}), got {np.shape(query_sets[0])}")
+                offs = np.ascontiguousarray(o, dtype=np.int64)
+                if offs.size < 1:
+                    raise ValueError("set_offsets needs n_sets + 1 entries")
+                return q, offs
+        return pack_query_sets(query_sets, self.dim)
+
+    def search_maxsim(self, query_sets, n_group_slots: int, k: int, row_mask: Optional[np.ndarray] = None,
+                      with_sums: bool = False):
+        """include/vdb.h vdb_index_search_maxsim, host memory: for each set of query vectors the ``k``
+        groups (``set_groups``; their ids must lie in [0, ``n_group_slots``)) with the greatest sum,
+        over the set's vectors, of the vector's best canonical key among the group's rows, by (sum
+        desc, group id asc).  ``query_sets`` is a sequence of sets, each [m, dim], or the packed tuple
+        ``(Q, offsets)``.  Returns (scores f32 [S,k], groups i32 [S,k][, sums f64 [S,k]]), the scores
+        in key units; slots past min(k, candidates) are 0 / -1 / -inf.  A set of more than 64
+        vectors, ``k`` outside [1, 128] or a bad ``n_group_slots`` raises ValueError."""
+        q, offs = self._maxsim_sets(query_sets)
+        n_sub, S = q.shape[0], offs.size - 1
+        k = int(k)
+        scores = np.empty((S, max(k, 0)), dtype=np.float32)  # (a bad k is the library's to refuse)
+        grp = np.empty((S, max(k, 0)), dtype=np.int32)
+        sums = np.empty((S, max(k, 0)), dtype=np.float64) if with_sums else None
+        mask_p = None
+        if row_mask is not None:
+            m = np.ascontiguousarray(row_mask, dtype=np.uint32)
+            need = (self.count() + 31) // 32
+            if m.size < need:
+                raise ValueError(f"row_mask needs {need} uint32 words, got {m.size}")
+            mask_p = _ptr(m)
+        _check(self._lib.vdb_index_search_maxsim(
+            self._h, _ptr(q) if n_sub else None, n_sub, _ptr(offs), S, int(n_group_slots), k, mask_p, MEM_HOST,
+            _ptr(scores), _ptr(grp), _ptr(sums) if sums is not None else None, None))
+        return (scores, grp, sums) if with_sums else (scores, grp)
+
+    def search_maxsim_device(self, q_ptr: int, n_sub: int, set_offsets_ptr: int, n_sets: int, n_group_slots: int,
+                             k: int, out_scores_ptr: int, out_groups_ptr: int, out_sums_ptr: int = 0,
+                             mask_ptr: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_maxsim with device-memory arguments (fp32 queries, int64 offsets);
+        stream-ordered, the offsets are not validated on the host and nothing is read back (a bad set
+        comes back empty and counts in stat ``maxsim_bad_sets``)."""
+        _check(self._lib.vdb_index_search_maxsim(
+            self._h, ctypes.c_void_p(q_ptr or None), int(n_sub), ctypes.c_void_p(set_offsets_ptr or None), int(n_sets),
+            int(n_group_slots), int(k), ctypes.c_void_p(mask_ptr or None), MEM_DEVICE,
+            ctypes.c_void_p(out_scores_ptr or None), ctypes.c_void_p(out_groups_ptr or None),
+            ctypes.c_void_p(out_sums_ptr or None), ctypes.c_void_p(stream or None)))
 
 
 class NativeShards:

@@ -63,6 +63,12 @@ REC_MAX_EXAMPLES = 64
 FUSED_MAX_K = 200
 FUSED_MAX_FETCH = 200
 FUSED_MAX_LISTS = 16
+# maxsim_query: the most groups per set, the most vectors per set and the most table entries (query
+# vectors of a call x distinct group values) of one device call (include/vdb.h
+# vdb_index_search_maxsim); POST /vectors/maxsim_query answers a value outside them with 400
+MAXSIM_MAX_K = 128
+MAXSIM_MAX_VECTORS = 64
+MAXSIM_MAX_CELLS = 1 << 27
 
 
 # half the smallest measured crossover of the row-list search against the masked
@@ -1072,6 +1078,72 @@ class MLXVectorStore:
                             [meta[i] if i < len(meta) else {} for i in ib], fused[b][valid].tolist(),
                             hits[b][valid].tolist()))
             return out
+
+    # ---- MaxSim query ------------------------------------------------------------------
+    def maxsim_query(self, query_vectors: Union[np.ndarray, Any], group_by: str, k: int = 10,
+                     filter_metadata: Optional[Dict] = None) -> List[Dict]:
+        """Late-interaction ("MaxSim": ColBERT / ColPali token embeddings) retrieval: the ``k`` best
+        values of the metadata key ``group_by`` for a set of query vectors [T, dim], T <= 64 -> a
+        list of ``{"group": value, "score": float, "sum": float}``, best first.  A group's sum is,
+        over the query vectors, the vector's best exact key among the group's rows (cosine
+        similarity; minus the SQUARED distance for euclidean), added in vector order in fp64;
+        ``score`` is that sum rounded to fp32.  Ties go to the group seen first in the store; rows
+        without the key belong to no group.  Exact over the whole corpus and the same for every
+        precision (include/vdb.h vdb_index_search_maxsim).  The reference has no such read."""
+        q = _as_matrix(query_vectors)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError(f"maxsim_query takes one set of vectors of shape (T, dim), got {q.shape}; "
+                             "use batch_maxsim_query for several sets")
+        return self.batch_maxsim_query([q], group_by, k, filter_metadata)[0]
+
+    def batch_maxsim_query(self, query_sets, group_by: str, k: int = 10,
+                           filter_metadata: Optional[Dict] = None) -> List[List[Dict]]:
+        """``maxsim_query`` for a list of query sets from one device call: one list of groups per
+        set."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("MaxSim query is not supported on a multi-device store")
+        k = int(k)
+        if not 1 <= k <= MAXSIM_MAX_K:
+            raise ValueError(f"k must be in [1, {MAXSIM_MAX_K}], got {k}")
+        sets = []
+        for s in query_sets:
+            a = _as_matrix(s)
+            if a.size == 0:  # a set without a vector: no error, no result
+                a = np.zeros((0, 0), np.float32)
+            elif a.ndim == 1:
+                a = a[None, :]
+            if a.ndim != 2:
+                raise ValueError(f"a query set must be 2-D (T, dim), got {a.shape}")
+            if a.shape[0] > MAXSIM_MAX_VECTORS:
+                raise ValueError(f"a query set takes at most {MAXSIM_MAX_VECTORS} vectors, got {a.shape[0]}")
+            sets.append(a)
+        B = len(sets)
+        empty = [[] for _ in range(B)]
+        with _Read(self._rw):
+            # (never the graph path, never the coalescer: one exact device call for all sets)
+            if self._vector_count == 0 or B == 0:
+                return empty
+            dim = self._dim
+            for a in sets:
+                if a.shape[0] and a.shape[1] != dim:
+                    raise ValueError(f"Dimension mismatch: query has {a.shape[1]} dims, store holds {dim}")
+            Q, offs = _vdb.pack_query_sets(sets, dim)
+            mask = self._range_mask(Q, filter_metadata)  # None: no filter; False: nothing to search
+            if mask is False:
+                return empty
+            with self._group_lock:  # one attached column: attach and search as one step
+                values = self._attach_groups(group_by)
+                if not values:  # no row has the key
+                    return empty
+                if Q.shape[0] and len(values) > MAXSIM_MAX_CELLS // Q.shape[0]:
+                    raise ValueError(f"{Q.shape[0]} query vectors x {len(values)} groups pass the "
+                                     f"{MAXSIM_MAX_CELLS} table entries of one call; send fewer sets at a time")
+                scores, grp, sums = self._index.search_maxsim((Q, offs), len(values), k, row_mask=mask, with_sums=True)
+            return [[{"group": values[g], "score": float(sc), "sum": float(sm)}
+                     for g, sc, sm in zip(grp[b][grp[b] >= 0].tolist(), scores[b][grp[b] >= 0].tolist(),
+                                          sums[b][grp[b] >= 0].tolist())] for b in range(B)]
 
     # ---- recommend --------------------------------------------------------------------
     def recommend(self, positive, negative=None, k: int = 10, filter_metadata: Optional[Dict] = None,
