@@ -155,7 +155,10 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * there; vdb_index_search_mmr's are "mmr_searches", "mmr_queries"; vdb_index_search_recommend's
  * "recommend_searches", "recommend_queries", "recommend_bad_queries"; vdb_index_search_fused's
  * "fused_searches", "fused_sets", "fused_bad_sets"; vdb_index_search_maxsim's "maxsim_searches",
- * "maxsim_sets", "maxsim_bad_sets", "maxsim_skipped_rows").  Stats also: "searches", "queries",
+ * "maxsim_sets", "maxsim_bad_sets", "maxsim_skipped_rows") and "sparse_wgs" (workgroups per query
+ * of vdb_index_search_sparse, 0 = auto; the sparse and hybrid calls' stats "sparse_rows",
+ * "sparse_nnz", "sparse_sets", "sparse_searches", "sparse_queries", "sparse_bad_queries",
+ * "hybrid_searches", "hybrid_queries" are described there).  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -568,6 +571,83 @@ int32_t vdb_index_search_fused(vdb_index* idx, const float* queries, int32_t n_s
                                const uint32_t* row_mask, int32_t mem,
                                float* out_scores, int64_t* out_indices, double* out_fused, int32_t* out_hits,
                                int64_t index_offset, void* stream);
+
+/* --- Hybrid search: a sparse vector per row, exact sparse top-k, RRF with dense ------
+ * Replaces: nothing the reference has.  The models of vdb_index_search_fused (Milvus' hybrid_search
+ * with RRFRanker, Qdrant's prefetch + fusion, LangChain's EnsembleRetriever) are mostly used to fuse
+ * a dense retriever with a sparse, lexical one (BM25, SPLADE or BGE-M3 term weights).  These three
+ * calls hold a sparse vector per row, rank by it exactly, and fuse that ranking with the dense one on
+ * the device.  Weighting (BM25 itself) is the caller's: the store keeps the weights it is given.
+ *
+ * vdb_index_set_sparse attaches one sparse vector per stored row, in CSR form: row r's entries are
+ * [indptr[r], indptr[r + 1]) of terms (int32) / weights (fp32).  Required, else VDB_ERR_INVALID (a NaN
+ * or Inf weight: VDB_ERR_NONFINITE): n == count; indptr ascending from 0 to nnz; term ids in [0,
+ * n_terms) and strictly ascending within a row; 1 <= n_terms <= 2^31 - 1.  A row without entries is
+ * valid.  indptr == NULL with n == 0 detaches the column.  Validation runs before the column is
+ * replaced (a device-memory call: by a kernel, one flag word read back); on any error the column
+ * attached before stays exactly as it was.  The call takes the exclusive lock, waits for queued
+ * searches, copies the column (the caller's arrays may be reused on return) and returns when done.
+ * Every successful add, remove and clear drops the column; vdb_index_update keeps it; it and the group
+ * column are independent.  The device copy interleaves (term, weight) as 8-byte pairs.  Stats:
+ * "sparse_rows" (rows attached, 0 = none), "sparse_nnz", "sparse_sets" (cumulative).
+ *
+ * vdb_index_search_sparse: the k best rows of each sparse query.
+ *   q_indptr     [n_queries + 1] int64, q_terms / q_weights [q_nnz]: the queries in CSR form.  A query
+ *                has at most 1 024 terms, ids strictly ascending in [0, n_terms), weights finite.
+ *   q_nnz        host scalar, so a device-memory call reads nothing back
+ *   k            1..1024
+ *   out_scores   [n_queries, k] fp32; out_indices [n_queries, k] int64; out_keys NULL or fp64
+ *   row_mask, mem, index_offset, stream: as vdb_index_search_rows; all pointers of one memory kind.
+ * Contract (every operation a separate fp64 operation): qd[t] = the query's weight for term t as a
+ * double, 0.0 for a term it does not list.  For row r: acc = 0.0; for the row's entries e in stored
+ * order acc = acc + (double)w_e * qd[t_e]; the sum is the key.  Row r matches when some entry has w_e
+ * != 0 and qd[t_e] != 0.  Candidates: the matching rows whose mask bit is set (a row that matches
+ * nothing is never returned, whatever its key).  Ranking by (key desc, row asc); the first min(k,
+ * candidates) are written: out_indices = row + index_offset, out_keys = key, out_scores = (float)key
+ * (round to nearest even).  Slots past that hold index -1 / score 0 / key -inf.  The key is a dot
+ * product whatever the index's metric; the result is the same bytes for every precision setting and
+ * both memory kinds (the dense rows and the candidate copies are not read).
+ * Errors, before anything is launched, both memory kinds: no sparse column attached, k outside [1,
+ * 1024], n_queries or q_nnz < 0, a NULL q_indptr / out_scores / out_indices with n_queries > 0, a bad
+ * mem -> VDB_ERR_INVALID.  Host-memory calls also: offsets that decrease or pass q_nnz, a query of
+ * more than 1 024 terms, a term id out of range or not above its predecessor -> VDB_ERR_INVALID; a
+ * NaN or Inf weight -> VDB_ERR_NONFINITE (no stat moves).  Device-memory calls are stream-ordered and
+ * read nothing back, so the kernel takes any input: offsets are clamped to [0, q_nnz] and nothing out
+ * of bounds is read; a query whose offsets the clamp changed or that decrease, that is too long or
+ * holds a bad term id or a non-finite weight is answered with all slots "no result" and counted on
+ * the device in stat "sparse_bad_queries"; the other queries are unaffected.  n_queries == 0 is
+ * VDB_OK; a query without terms is no error (all its slots "no result"); an empty index with an empty
+ * column attached gives "no result" everywhere.  Takes the shared lock and a per-search workspace, as
+ * vdb_index_search_rows does.  Knob "sparse_wgs": workgroups per query, 0 = auto (results identical).
+ * Stats: "sparse_searches", "sparse_queries", "sparse_bad_queries"; "searches" / "queries" and every
+ * "searches_*" stat stay still.
+ *
+ * vdb_index_search_hybrid: query b is the fused-search set whose list 0 is what vdb_index_search
+ * returns for queries[b] with k = fetch_k and row_mask, whose list 1 is what vdb_index_search_sparse
+ * returns for sparse query b with k = fetch_k and row_mask, whose weights are (w_dense, w_sparse) and
+ * whose fusion is VDB_FUSE_RRF with rrf_c; the outputs are as vdb_index_search_fused defines them
+ * (out_hits 1 or 2; ties to the lower row).  1 <= k <= fetch_k <= 200; w_dense, w_sparse and rrf_c
+ * finite and >= 0; out_fused and out_hits may be NULL.  With w_sparse == 0 the first k rows are those
+ * of the dense search, in its order; a query with no sparse terms, or with none matching, ranks by its
+ * dense list alone.  Same bytes for every precision setting and both memory kinds.  Errors: those of
+ * the two inner calls and those checks, before anything is launched; a device-memory query the sparse
+ * kernel finds bad contributes an empty sparse list (counted in "sparse_bad_queries") and its dense
+ * list still ranks.  Stats: "hybrid_searches", "hybrid_queries"; "searches" / "queries" move once per
+ * call through the inner dense search; "sparse_searches" / "sparse_queries" stay still. */
+int32_t vdb_index_set_sparse(vdb_index* idx, const int64_t* indptr, const int32_t* terms, const float* weights,
+                             int64_t n, int64_t nnz, int32_t n_terms, int32_t mem, void* stream);
+int32_t vdb_index_search_sparse(vdb_index* idx, const int64_t* q_indptr, const int32_t* q_terms, const float* q_weights,
+                                int32_t n_queries, int64_t q_nnz, int32_t k,
+                                const uint32_t* row_mask, int32_t mem,
+                                float* out_scores, int64_t* out_indices, double* out_keys,
+                                int64_t index_offset, void* stream);
+int32_t vdb_index_search_hybrid(vdb_index* idx, const float* queries,
+                                const int64_t* q_indptr, const int32_t* q_terms, const float* q_weights,
+                                int32_t n_queries, int64_t q_nnz,
+                                int32_t k, int32_t fetch_k, double w_dense, double w_sparse, double rrf_c,
+                                const uint32_t* row_mask, int32_t mem,
+                                float* out_scores, int64_t* out_indices, double* out_fused, int32_t* out_hits,
+                                int64_t index_offset, void* stream);
 
 /* --- MaxSim search: groups ranked by the summed best match per query vector ---------
  * Replaces: nothing the reference has.  Multi-vector ("late interaction") retrieval -- ColBERT /

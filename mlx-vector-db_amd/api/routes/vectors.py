@@ -97,6 +97,43 @@ class VectorFusedQuery(BaseModel):
     filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
 
 
+class SparseVector(BaseModel):
+    """A sparse vector: term ids and their weights (BM25, SPLADE or BGE-M3 term weights)."""
+    indices: List[int]
+    values: List[float]
+
+
+class VectorSparseQuery(BaseModel):
+    """The ``k`` rows whose sparse vector (stored in the row's metadata under ``sparse_key``) has the
+    greatest dot product with ``sparse``; only rows sharing a term with it are returned.  The store
+    checks the limits (k at most 1024, at most 1024 terms, no repeated index); a value outside them
+    is a 400."""
+    user_id: str
+    model_id: str
+    sparse: SparseVector = Field(..., description="The query's sparse vector")
+    k: int = Field(default=10, description="Rows returned")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    sparse_key: str = Field(default="sparse", description="Metadata key holding each row's sparse vector")
+
+
+class VectorHybridQuery(BaseModel):
+    """Dense and sparse retrieval fused by weighted reciprocal rank: the best ``fetch_k`` rows (null:
+    min(200, max(k, 4 k))) for ``query`` and the best ``fetch_k`` for ``sparse`` are fused per row,
+    ``weights[0] / (rrf_c + dense rank) + weights[1] / (rrf_c + sparse rank)``.  The store checks the
+    limits (k and fetch_k at most 200, fetch_k >= k, two weights finite and >= 0); a value outside
+    them is a 400."""
+    user_id: str
+    model_id: str
+    query: List[float] = Field(..., description="The dense query vector")
+    sparse: SparseVector = Field(..., description="The query's sparse vector")
+    k: int = Field(default=10, description="Rows returned")
+    fetch_k: Optional[int] = Field(default=None, description="Rows fetched per retriever")
+    weights: List[float] = Field(default=[1.0, 1.0], description="(dense weight, sparse weight)")
+    rrf_c: float = Field(default=60.0, description="The constant added to a rank")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    sparse_key: str = Field(default="sparse", description="Metadata key holding each row's sparse vector")
+
+
 class VectorMaxSimQuery(BaseModel):
     """Late-interaction ("MaxSim") retrieval: the ``k`` best values of the metadata key ``group_by``
     (documents of a multi-vector corpus) for a set of query vectors (token embeddings).  A group's
@@ -209,6 +246,20 @@ class VectorFusedQueryResponse(BaseModel):
     # "similarity_score" and "distance" of the best-matching vector
     results: List[Dict[str, Any]]
     fusion: str
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorSparseQueryResponse(BaseModel):
+    # best first: {"metadata", "sparse_score" (the dot product), "rank"}
+    results: List[Dict[str, Any]]
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorHybridQueryResponse(BaseModel):
+    # best first: {"metadata", "fused_score", "hits" (1 or 2: the retrievers that returned the row), "rank"}
+    results: List[Dict[str, Any]]
     query_time_ms: float
     total_vectors_searched: int
 
@@ -518,6 +569,63 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in fused query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Fused query failed: {e}")
+
+    @router.post("/sparse_query", response_model=VectorSparseQueryResponse)
+    async def sparse_query_vectors(request: VectorSparseQuery, api_key: str = Depends(auth)):
+        """The ``k`` rows with the greatest sparse dot product, best first.  A bad request (k outside
+        its limits, a repeated index, too many terms: the store's ValueError) is a 400, an
+        unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            sparse = {"indices": request.sparse.indices, "values": request.sparse.values}
+            loop = asyncio.get_running_loop()
+            indices, scores, metas = await loop.run_in_executor(
+                mgr._executor, lambda: store.sparse_query(sparse, k=request.k, filter_metadata=request.filter_metadata,
+                                                          sparse_key=request.sparse_key))
+            results = [{"metadata": m, "sparse_score": s, "rank": i + 1} for i, (m, s) in enumerate(zip(metas, scores))]
+            return VectorSparseQueryResponse(results=results, query_time_ms=(time.time() - t0) * 1000,
+                                             total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Sparse query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Sparse query failed: {e}")
+        except Exception as e:
+            logger.error("Error in sparse query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Sparse query failed: {e}")
+
+    @router.post("/hybrid_query", response_model=VectorHybridQueryResponse)
+    async def hybrid_query_vectors(request: VectorHybridQuery, api_key: str = Depends(auth)):
+        """Dense and sparse retrieval fused by weighted reciprocal rank, best first.  A bad request
+        (no vector, k / fetch_k / rrf_c / weights outside their limits, a bad sparse vector, dimension
+        mismatch: the store's ValueError) is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if not request.query:
+                raise HTTPException(status_code=400, detail="Query vector required")
+            sparse = {"indices": request.sparse.indices, "values": request.sparse.values}
+            loop = asyncio.get_running_loop()
+            indices, scores, metas, fused, hits = await loop.run_in_executor(
+                mgr._executor, lambda: store.hybrid_query(request.query, sparse, k=request.k, fetch_k=request.fetch_k,
+                                                          weights=request.weights, rrf_c=request.rrf_c,
+                                                          filter_metadata=request.filter_metadata,
+                                                          sparse_key=request.sparse_key))
+            results = [{"metadata": m, "fused_score": f, "hits": h, "rank": i + 1}
+                       for i, (m, f, h) in enumerate(zip(metas, fused, hits))]
+            return VectorHybridQueryResponse(results=results, query_time_ms=(time.time() - t0) * 1000,
+                                             total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Hybrid query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Hybrid query failed: {e}")
+        except Exception as e:
+            logger.error("Error in hybrid query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Hybrid query failed: {e}")
 
     @router.post("/maxsim_query", response_model=VectorMaxSimQueryResponse)
     async def maxsim_query_vectors(request: VectorMaxSimQuery, api_key: str = Depends(auth)):

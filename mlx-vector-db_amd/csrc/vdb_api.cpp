@@ -30,6 +30,7 @@
 #include "vdb_mmr_plan.h"
 #include "vdb_fuse_plan.h"
 #include "vdb_maxsim_plan.h"
+#include "vdb_sparse_plan.h"
 #include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
 #include "vdb_internal.h"
@@ -66,6 +67,8 @@ constexpr int kRecommendBadWord = 13;     // d_xmax word counting the queries a 
 constexpr int kFusedBadWord = 14;         // d_xmax word counting the sets a fused search found bad on the device
 constexpr int kMaxsimBadWord = 24;        // d_xmax word counting the sets a MaxSim search found bad on the device
 constexpr int kMaxsimSkippedWord = 25;    // d_xmax word counting the rows MaxSim searches skipped for an id past the slots
+constexpr int kSparseBadWord = 26;        // d_xmax word counting the queries a sparse search found bad on the device
+constexpr int kSparseFlagWord = 27;       // d_xmax word a device-memory vdb_index_set_sparse's validation writes its causes to
 constexpr size_t kXmaxBytes = 256;        // d_xmax in all (layout: vdb_index_create)
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
@@ -268,6 +271,19 @@ struct vdb_index {
     // vdb_index_search_maxsim: calls and sets (successful calls); the sets its rank kernel found bad
     // and the rows its scan skipped are counted on the device (d_xmax + kMaxsimBadWord / SkippedWord)
     std::atomic<int64_t> n_maxsim_searches{0}, n_maxsim_sets{0};
+    // vdb_index_set_sparse: the sparse column, one CSR row per stored row (device copies owned by the
+    // index): sparse_indptr [sparse_n + 1] and sparse_pairs [sparse_nnz] interleaved (term, weight);
+    // add, remove and clear drop it (sparse_set = false), update keeps it; independent of the groups
+    int64_t* sparse_indptr = nullptr;
+    SparsePair* sparse_pairs = nullptr;
+    int64_t sparse_n = 0, sparse_nnz = 0;
+    int32_t sparse_terms = 0;
+    bool sparse_set = false;
+    int64_t sparse_wgs = 0;  // knob: workgroups per query of a sparse search (0 = auto)
+    // vdb_index_search_sparse / _hybrid: calls and queries (successful calls); the queries the sparse
+    // kernel found bad are counted on the device (d_xmax + kSparseBadWord)
+    std::atomic<int64_t> n_sparse_sets{0}, n_sparse_searches{0}, n_sparse_queries{0};
+    std::atomic<int64_t> n_hybrid_searches{0}, n_hybrid_queries{0};
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -879,7 +895,9 @@ int32_t vdb_index_create(int32_t dim, int32_t metric, int32_t device, vdb_index*
     // [104, 112) the queries recommend searches flagged (kRecommendBadWord; likewise),
     // [112, 120) the sets fused searches found bad (kFusedBadWord; likewise),
     // [192, 200) the sets MaxSim searches found bad and [200, 208) the rows they skipped
-    // (kMaxsimBadWord, kMaxsimSkippedWord; likewise)
+    // (kMaxsimBadWord, kMaxsimSkippedWord; likewise), [208, 216) the queries sparse searches found
+    // bad (kSparseBadWord; likewise), [216, 224) the causes of a device-memory vdb_index_set_sparse
+    // (kSparseFlagWord; zeroed by each such call)
     if (e == hipSuccess) e = hipMalloc(&ix->d_xmax, kXmaxBytes);
     if (e == hipSuccess) e = zero_now(ix->d_xmax, kXmaxBytes, ix->stream);
     if (e == hipSuccess) e = hipMalloc(&ix->d_i8, 64);
@@ -933,6 +951,8 @@ int32_t vdb_index_destroy(vdb_index* ix) {
     if (ix->groups) (void)hipFree(ix->groups);
     if (ix->group_valid) (void)hipFree(ix->group_valid);
     if (ix->d_group_fb) (void)hipFree(ix->d_group_fb);
+    if (ix->sparse_indptr) (void)hipFree(ix->sparse_indptr);
+    if (ix->sparse_pairs) (void)hipFree(ix->sparse_pairs);
     if (ix->h_totals) (void)hipHostFree(ix->h_totals);
     for (auto& kv : ix->uses) (void)hipEventDestroy(kv.second);
     if (ix->stream) (void)hipStreamDestroy(ix->stream);
@@ -1066,6 +1086,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "subset_wgs must be in [0, %d] (0 = auto)", kSubsetMaxSeg);
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->subset_wgs = value;
+    } else if (n == "sparse_wgs") {
+        if (value < 0 || value > kSparseMaxSeg)
+            return set_error(VDB_ERR_INVALID, "sparse_wgs must be in [0, %d] (0 = auto)", kSparseMaxSeg);
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->sparse_wgs = value;
     } else if (n == "group_fetch") {
         if (value < 0 || value > kGroupMaxFetch)
             return set_error(VDB_ERR_INVALID, "group_fetch must be in [0, %d] (0 = auto)", kGroupMaxFetch);
@@ -1209,6 +1234,21 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
         HIP_TRY(hipMemcpy(&c, ix->d_xmax + (n == "maxsim_bad_sets" ? kMaxsimBadWord : kMaxsimSkippedWord), sizeof(c),
                           hipMemcpyDeviceToHost));
         *value = (int64_t)c;
+    }
+    else if (n == "sparse_rows") *value = ix->sparse_set ? ix->sparse_n : 0;
+    else if (n == "sparse_nnz") *value = ix->sparse_set ? ix->sparse_nnz : 0;
+    else if (n == "sparse_sets") *value = ix->n_sparse_sets.load();
+    else if (n == "sparse_searches") *value = ix->n_sparse_searches.load();
+    else if (n == "sparse_queries") *value = ix->n_sparse_queries.load();
+    else if (n == "hybrid_searches") *value = ix->n_hybrid_searches.load();
+    else if (n == "hybrid_queries") *value = ix->n_hybrid_queries.load();
+    else if (n == "sparse_bad_queries") {  // counted by the sparse kernel: after the searches queued so far
+        HIP_TRY(hipSetDevice(ix->device));
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpy(&bad, ix->d_xmax + kSparseBadWord, sizeof(bad), hipMemcpyDeviceToHost));
+        *value = (int64_t)bad;
     }
     else if (n == "group_fallback_queries") {  // counted by the select kernel: after the searches queued so far
         unsigned long long fb = 0;
@@ -1397,6 +1437,7 @@ int32_t vdb_index_add(vdb_index* ix, const float* vectors, int64_t n, int32_t me
     ix->xres_dir = xm[3];
     ix->count += n;
     ix->group_set = false;  // the group column covered the old rows only
+    ix->sparse_set = false;  // and so did the sparse column
     ix->auto_hold = 0;  // new rows: VDB_PREC_AUTO tries the one-plane passes again
     ix->auto_fails = 0;
     ix->auto_hold8 = 0;
@@ -1436,6 +1477,7 @@ static int32_t clear_locked(vdb_index* ix) {
     std::memset(ix->i8st, 0, sizeof(ix->i8st));
     ix->count = 0;
     ix->group_set = false;
+    ix->sparse_set = false;
     ix->auto_hold = 0;
     ix->auto_fails = 0;
     ix->auto_hold8 = 0;
@@ -1579,6 +1621,7 @@ int32_t vdb_index_remove(vdb_index* ix, const uint32_t* remove_mask, int32_t mem
     (void)done(VDB_OK);
     ix->count = kept;
     ix->group_set = false;  // the rows moved: the group column no longer lines up
+    ix->sparse_set = false;  // nor does the sparse column
     ix->gen++;
     ix->n_rows_removed += N - kept;
     ix->auto_hold = 0;  // the rows changed: VDB_PREC_AUTO tries the one-plane passes again
@@ -3120,6 +3163,368 @@ int32_t vdb_index_search_fused(vdb_index* ix, const float* queries, int32_t n_su
     }
     ix->n_fused_searches++;
     ix->n_fused_sets += n_sets;
+    return VDB_OK;
+}
+
+int32_t vdb_index_set_sparse(vdb_index* ix, const int64_t* indptr, const int32_t* terms, const float* weights, int64_t n,
+                             int64_t nnz, int32_t n_terms, int32_t mem, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::shared_mutex> g(ix->mu);
+    switch (sparse_column_args(indptr != nullptr, terms != nullptr, weights != nullptr, n, nnz, n_terms, ix->count)) {
+        case kSparseColBadCounts:
+            return set_error(VDB_ERR_INVALID,
+                             indptr ? "the sparse column has %lld rows, the index %lld (nnz %lld >= 0 and n_terms %d >= 1 required)"
+                                    : "a NULL indptr detaches: n must be 0 (got %lld)",
+                             (long long)n, (long long)ix->count, (long long)nnz, n_terms);
+        case kSparseColNullPointer: return set_error(VDB_ERR_INVALID, "NULL terms / weights with nnz %lld", (long long)nnz);
+        default: break;
+    }
+    const bool host = mem == VDB_MEM_HOST;
+    const auto cause_error = [&](int cause, int64_t row, bool have_row) {
+        const char* what = cause == kSparseColBadIndptr  ? "indptr must ascend from 0 to nnz"
+                           : cause == kSparseColBadTerm  ? "a term id outside [0, n_terms)"
+                           : cause == kSparseColUnsorted ? "term ids must be strictly ascending within a row"
+                                                         : "a NaN or Inf weight";
+        const int code = cause == kSparseColNonFinite ? VDB_ERR_NONFINITE : VDB_ERR_INVALID;
+        return have_row ? set_error(code, "sparse column, row %lld: %s", (long long)row, what)
+                        : set_error(code, "sparse column: %s", what);
+    };
+    if (indptr && host) {  // everything checked before the column is replaced
+        int64_t at = 0;
+        const int cause = sparse_validate_column(indptr, terms, weights, n, nnz, n_terms, &at);
+        if (cause != kSparseColOk) return cause_error(cause, at, true);
+    }
+    // queued device-memory searches on caller streams read the column this call replaces
+    {
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+    }
+    if (!indptr) {  // detach
+        ix->sparse_set = false;
+        return VDB_OK;
+    }
+    // the new column is built beside the old one, which stays as it was on any error
+    hipStream_t st = ix->stream;
+    int64_t* ind_new = nullptr;
+    SparsePair* pairs_new = nullptr;
+    HIP_TRY(hipMalloc(&ind_new, (size_t)(n + 1) * sizeof(int64_t)));
+    {
+        const hipError_t e = hipMalloc(&pairs_new, (size_t)std::max<int64_t>(nnz, 1) * sizeof(SparsePair));
+        if (e != hipSuccess) {
+            (void)hipFree(ind_new);
+            HIP_TRY(e);
+        }
+    }
+    const auto build = [&]() -> int {
+        if (host) {
+            std::vector<SparsePair> pairs((size_t)nnz);
+            for (int64_t e = 0; e < nnz; ++e) pairs[(size_t)e] = SparsePair{terms[e], weights[e]};
+            HIP_TRY(hipMemcpyAsync(ind_new, indptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            if (nnz > 0)
+                HIP_TRY(hipMemcpyAsync(pairs_new, pairs.data(), (size_t)nnz * sizeof(SparsePair), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            return VDB_OK;
+        }
+        // device memory: the arrays may still be being written on the caller's stream; a kernel
+        // validates them and one flag word comes back, as vdb_index_update's does
+        HIP_TRY(order_after_caller(st, stream));
+        uint32_t* flags = reinterpret_cast<uint32_t*>(ix->d_xmax + kSparseFlagWord);
+        HIP_TRY(hipMemsetAsync(flags, 0, sizeof(unsigned long long), st));
+        HIP_TRY(hipMemcpyAsync(ind_new, indptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(launch_sparse_validate(ind_new, terms, weights, n, nnz, n_terms, flags, st));
+        uint32_t hflags[2] = {0, 0};
+        int64_t first = 0;
+        HIP_TRY(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, st));
+        if (n == 0) HIP_TRY(hipMemcpyAsync(&first, ind_new, sizeof(first), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n == 0 && (first != 0 || nnz != 0)) return cause_error(kSparseColBadIndptr, 0, false);
+        const int cause = sparse_column_cause(hflags[0]);
+        if (cause != kSparseColOk) return cause_error(cause, 0, false);
+        HIP_TRY(launch_sparse_pack(terms, weights, nnz, pairs_new, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return VDB_OK;
+    };
+    const int rc = build();
+    if (rc) {
+        (void)hipFree(ind_new);
+        (void)hipFree(pairs_new);
+        return rc;
+    }
+    if (ix->sparse_indptr) (void)hipFree(ix->sparse_indptr);
+    if (ix->sparse_pairs) (void)hipFree(ix->sparse_pairs);
+    ix->sparse_indptr = ind_new;
+    ix->sparse_pairs = pairs_new;
+    ix->sparse_n = n;
+    ix->sparse_nnz = nnz;
+    ix->sparse_terms = n_terms;
+    ix->sparse_set = true;
+    ix->n_sparse_sets++;
+    return VDB_OK;
+}
+
+namespace {
+// What a sparse or hybrid call's validation found, as the error the call returns.
+int sparse_call_error(int cause, int k, int fetch_k, int64_t at) {
+    switch (cause) {
+        case kSparseBadCounts: return set_error(VDB_ERR_INVALID, "n_queries and q_nnz must be >= 0");
+        case kSparseBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", fetch_k ? kFuseMaxK : kSparseMaxK, k);
+        case kSparseNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/output pointer");
+        case kSparseBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind");
+        case kSparseNoColumn: return set_error(VDB_ERR_INVALID, "no sparse column is attached (vdb_index_set_sparse)");
+        case kSparseBadOffsets:
+            return set_error(VDB_ERR_INVALID, "q_indptr[%lld]: offsets must ascend from >= 0 to <= q_nnz", (long long)at);
+        case kSparseTooLong:
+            return set_error(VDB_ERR_INVALID, "query %lld has more than %d terms", (long long)at, kSparseMaxQueryTerms);
+        case kSparseBadTerm: return set_error(VDB_ERR_INVALID, "q_terms[%lld] is outside [0, n_terms)", (long long)at);
+        case kSparseUnsorted:
+            return set_error(VDB_ERR_INVALID, "q_terms[%lld]: a query's term ids must be strictly ascending", (long long)at);
+        case kSparseNonFinite: return set_error(VDB_ERR_NONFINITE, "q_weights[%lld] is NaN or Inf", (long long)at);
+        case kHybridBadFetch:
+            return set_error(VDB_ERR_INVALID, "fetch_k must be in [k, %d], got fetch_k=%d k=%d", kFuseMaxFetch, fetch_k, k);
+        case kHybridBadWeight: return set_error(VDB_ERR_INVALID, "w_dense and w_sparse must be finite and >= 0");
+        case kHybridBadC: return set_error(VDB_ERR_INVALID, "rrf_c must be finite and >= 0");
+        default: return VDB_OK;
+    }
+}
+}  // namespace
+
+int32_t vdb_index_search_sparse(vdb_index* ix, const int64_t* q_indptr, const int32_t* q_terms, const float* q_weights,
+                                int32_t B, int64_t q_nnz, int32_t k, const uint32_t* row_mask, int32_t mem,
+                                float* out_scores, int64_t* out_indices, double* out_keys, int64_t index_offset,
+                                void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // everything checked before any launch (a device-memory call's queries: by the kernel)
+    const bool column = ix->sparse_set && ix->sparse_n == N;
+    int cause = sparse_validate_call(B, q_nnz, k, q_indptr != nullptr, q_terms != nullptr, q_weights != nullptr,
+                                     out_scores != nullptr, out_indices != nullptr, mem, column);
+    if (cause) return sparse_call_error(cause, k, 0, 0);
+    if (B == 0) return VDB_OK;
+    const bool host = mem == VDB_MEM_HOST;
+    if (host) {
+        int64_t at = 0;
+        cause = sparse_validate_queries(q_indptr, q_terms, q_weights, B, q_nnz, ix->sparse_terms, &at);
+        if (cause) return sparse_call_error(cause, k, 0, at);
+    }
+    // as vdb_index_search_rows: the caller's stream (device memory: NULL = the null stream), or for
+    // a host-memory call without one the stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const int KE = sparse_ke(k);
+    const int n_seg = N > 0 ? sparse_n_seg(ix->sparse_wgs, N, B, ix->n_cu) : 1;
+    const SparseScratch sc = sparse_scratch(B, k, n_seg, q_nnz, N, host, masked, out_keys != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    SparseArgs a{};
+    a.q_indptr = q_indptr;
+    a.q_terms = q_terms;
+    a.q_weights = q_weights;
+    a.mask = masked ? row_mask : nullptr;
+    a.out_s = out_scores;
+    a.out_i = out_indices;
+    a.out_k = out_keys;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.indptr - sc.in0), q_indptr, ((size_t)B + 1) * 8);
+            if (q_nnz > 0) {
+                std::memcpy(h + (sc.terms - sc.in0), q_terms, (size_t)q_nnz * 4);
+                std::memcpy(h + (sc.weights - sc.in0), q_weights, (size_t)q_nnz * 4);
+            }
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+        });
+        if (rc) return rc;
+        a.q_indptr = reinterpret_cast<const int64_t*>(dev + sc.indptr);
+        a.q_terms = reinterpret_cast<const int32_t*>(dev + sc.terms);
+        a.q_weights = reinterpret_cast<const float*>(dev + sc.weights);
+        a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_k = out_keys ? reinterpret_cast<double*>(dev + sc.out_k) : nullptr;
+    }
+    a.indptr = ix->sparse_indptr;
+    a.pairs = ix->sparse_pairs;
+    a.N = N;
+    a.n_terms = ix->sparse_terms;
+    a.q_nnz = q_nnz;
+    a.k = k;
+    a.KE = KE;
+    a.out_ld = k;
+    a.done = reinterpret_cast<int*>(dev + sc.done);
+    a.lk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.lk) : nullptr;
+    a.li = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.li) : nullptr;
+    a.mk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.mk) : nullptr;
+    a.mi = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.mi) : nullptr;
+    a.bad = ix->d_xmax + kSparseBadWord;
+    a.index_offset = index_offset;
+    // the per-query counters start at zero (the kernel leaves them so; a grown workspace is fresh)
+    if (n_seg > 1) HIP_TRY(hipMemsetAsync(a.done, 0, (size_t)B * sizeof(int), st));
+    // (an empty index: no row is read, every slot "no result"; a device call's bad queries still count)
+    HIP_TRY(launch_sparse_search(a, B, n_seg, st));
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+        if (out_keys) std::memcpy(out_keys, r + (sc.out_k - sc.out0), (size_t)B * k * 8);
+    }
+    ix->n_sparse_searches++;
+    ix->n_sparse_queries += B;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_hybrid(vdb_index* ix, const float* queries, const int64_t* q_indptr, const int32_t* q_terms,
+                                const float* q_weights, int32_t B, int64_t q_nnz, int32_t k, int32_t fetch_k,
+                                double w_dense, double w_sparse, double rrf_c, const uint32_t* row_mask, int32_t mem,
+                                float* out_scores, int64_t* out_indices, double* out_fused, int32_t* out_hits,
+                                int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // everything checked before any launch: the checks of the two inner calls and the fuse call's
+    const bool column = ix->sparse_set && ix->sparse_n == N;
+    int cause = hybrid_validate_call(B, q_nnz, k, fetch_k, w_dense, w_sparse, rrf_c, queries != nullptr, q_indptr != nullptr,
+                                     q_terms != nullptr, q_weights != nullptr, out_scores != nullptr,
+                                     out_indices != nullptr, mem, column);
+    if (cause) return sparse_call_error(cause, k, fetch_k, 0);
+    if (B == 0) return VDB_OK;
+    const int D = ix->dim;
+    const bool host = mem == VDB_MEM_HOST;
+    if (host) {
+        int64_t at = 0;
+        cause = sparse_validate_queries(q_indptr, q_terms, q_weights, B, q_nnz, ix->sparse_terms, &at);
+        if (cause) return sparse_call_error(cause, k, fetch_k, at);
+        if (!all_finite(queries, (int64_t)B * D)) return set_error(VDB_ERR_NONFINITE, "query contains NaN or Inf");
+    }
+    // as vdb_index_search_fused: the caller's stream, or for a host-memory call without one the
+    // stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const int F = fetch_k;
+    const int KE = sparse_ke(F);
+    const int n_seg = N > 0 ? sparse_n_seg(ix->sparse_wgs, N, B, ix->n_cu) : 1;
+    const HybridScratch sc = hybrid_scratch(B, D, k, F, n_seg, q_nnz, N, host, masked, out_fused != nullptr,
+                                            out_hits != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    const float* Qd = queries;
+    const uint32_t* md = masked ? row_mask : nullptr;
+    SparseArgs sa{};
+    sa.q_indptr = q_indptr;
+    sa.q_terms = q_terms;
+    sa.q_weights = q_weights;
+    FuseArgs a{};
+    a.out_s = out_scores; a.out_i = out_indices; a.out_f = out_fused; a.out_h = out_hits;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+            std::memcpy(h + (sc.indptr - sc.in0), q_indptr, ((size_t)B + 1) * 8);
+            if (q_nnz > 0) {
+                std::memcpy(h + (sc.terms - sc.in0), q_terms, (size_t)q_nnz * 4);
+                std::memcpy(h + (sc.weights - sc.in0), q_weights, (size_t)q_nnz * 4);
+            }
+            if (masked) {
+                std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+                std::memset(h + (sc.mask - sc.in0) + sc.mask_words * 4, 0, 64 * 4);
+            }
+        });
+        if (rc) return rc;
+        Qd = reinterpret_cast<const float*>(dev + sc.q);
+        md = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        sa.q_indptr = reinterpret_cast<const int64_t*>(dev + sc.indptr);
+        sa.q_terms = reinterpret_cast<const int32_t*>(dev + sc.terms);
+        sa.q_weights = reinterpret_cast<const float*>(dev + sc.weights);
+        a.out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_f = out_fused ? reinterpret_cast<double*>(dev + sc.out_f) : nullptr;
+        a.out_h = out_hits ? reinterpret_cast<int32_t*>(dev + sc.out_h) : nullptr;
+    }
+    float* ds = reinterpret_cast<float*>(dev + sc.ds);
+    int64_t* di = reinterpret_cast<int64_t*>(dev + sc.di);
+    double* dk = reinterpret_cast<double*>(dev + sc.dk);
+    float* fs = reinterpret_cast<float*>(dev + sc.fs);
+    int64_t* fi = reinterpret_cast<int64_t*>(dev + sc.fi);
+    double* fk = reinterpret_cast<double*>(dev + sc.fk);
+    int64_t* offs = reinterpret_cast<int64_t*>(dev + sc.offs);
+    double* wts = reinterpret_cast<double*>(dev + sc.w);
+    const bool inner = N > 0;
+    if (inner) {
+        // step 1: the dense lists, the best fetch_k eligible rows of every query with their scores and
+        // keys, by the ordinary search in device memory on this stream (its own workspace,
+        // certificate and gated fallback; it counts the call in "searches" / "queries")
+        SearchOpts o;
+        rc = search_locked(ix, Qd, B, F, md, VDB_MEM_DEVICE, ds, di, dk, 0, st, nullptr, o);
+        if (rc == kRetryBf16x3) {
+            o.force_b3 = true;
+            rc = search_locked(ix, Qd, B, F, md, VDB_MEM_DEVICE, ds, di, dk, 0, st, nullptr, o);
+        }
+        if (rc) return rc;
+        // step 2: into the even lists of the sets (list 2 b of [2 B][F]): three strided copies
+        HIP_TRY(hipMemcpy2DAsync(fs, (size_t)2 * F * 4, ds, (size_t)F * 4, (size_t)F * 4, B, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(fi, (size_t)2 * F * 8, di, (size_t)F * 8, (size_t)F * 8, B, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(fk, (size_t)2 * F * 8, dk, (size_t)F * 8, (size_t)F * 8, B, hipMemcpyDeviceToDevice, st));
+    }
+    // step 3: the sparse lists straight into the odd ones (an empty index: "no result" lists the fuse
+    // kernel does not read; a device-memory call's bad queries are still counted)
+    sa.indptr = ix->sparse_indptr;
+    sa.pairs = ix->sparse_pairs;
+    sa.N = N;
+    sa.n_terms = ix->sparse_terms;
+    sa.q_nnz = q_nnz;
+    sa.mask = md;
+    sa.k = F;
+    sa.KE = KE;
+    sa.out_s = fs + F;
+    sa.out_i = fi + F;
+    sa.out_k = fk + F;
+    sa.out_ld = 2 * (int64_t)F;
+    sa.done = reinterpret_cast<int*>(dev + sc.done);
+    sa.lk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.lk) : nullptr;
+    sa.li = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.li) : nullptr;
+    sa.mk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.mk) : nullptr;
+    sa.mi = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.mi) : nullptr;
+    sa.bad = ix->d_xmax + kSparseBadWord;
+    sa.index_offset = 0;
+    if (n_seg > 1) HIP_TRY(hipMemsetAsync(sa.done, 0, (size_t)B * sizeof(int), st));
+    HIP_TRY(launch_sparse_search(sa, B, n_seg, st));
+    // step 4: one workgroup per query fuses its two lists by weighted reciprocal rank
+    HIP_TRY(launch_hybrid_sets(offs, wts, B, w_dense, w_sparse, st));
+    a.fs = fs; a.fi = fi; a.fk = fk;
+    a.k_fetch = F; a.k = k; a.n_sub = 2 * (int64_t)B; a.rrf_c = rrf_c; a.count = N;
+    a.offs = offs; a.weights = wts;
+    a.bad = ix->d_xmax + kFusedBadWord;  // (never moved: the sets are built here)
+    a.index_offset = index_offset;
+    HIP_TRY(launch_fuse(kFuseRrf, a, B, st));
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+        if (out_fused) std::memcpy(out_fused, r + (sc.out_f - sc.out0), (size_t)B * k * 8);
+        if (out_hits) std::memcpy(out_hits, r + (sc.out_h - sc.out0), (size_t)B * k * 4);
+    }
+    if (!inner) {  // (otherwise the call was counted by its inner search)
+        ix->n_searches++;
+        ix->n_queries += B;
+    }
+    ix->n_hybrid_searches++;
+    ix->n_hybrid_queries += B;
     return VDB_OK;
 }
 

@@ -425,6 +425,38 @@ struct FuseArgs {
 };
 hipError_t launch_fuse(int fusion, const FuseArgs& a, int n_sets, hipStream_t st);
 
+// The sparse column and the sparse search (vdb_sparse.hip, vdb_index_set_sparse /
+// vdb_index_search_sparse / vdb_index_search_hybrid).  Validate: a device-memory column indptr [n +
+// 1] / terms / weights [nnz], read under the checks of vdb_sparse_plan.h whatever it holds; *flags |=
+// one bit per cause found (sparse_column_flag).  Pack: pairs[e] = (terms[e], weights[e]), e < nnz.
+struct SparsePair;
+hipError_t launch_sparse_validate(const int64_t* indptr, const int32_t* terms, const float* weights, int64_t n,
+                                  int64_t nnz, int32_t n_terms, uint32_t* flags, hipStream_t st);
+hipError_t launch_sparse_pack(const int32_t* terms, const float* weights, int64_t nnz, SparsePair* pairs,
+                              hipStream_t st);
+// Search: query b is entries [q_indptr[b], q_indptr[b + 1]) of q_terms / q_weights (q_nnz in all), in
+// device memory, read under the clamp and the checks of vdb_sparse_plan.h whatever they hold (*bad +=
+// the queries found bad).  Row r < N is a candidate when it matches the query and mask (optional, the
+// row_mask layout) has its bit; the best k by (key desc, row asc) go to out_* [b * out_ld + e], e < k
+// (out_k optional; out_ld >= k: the hybrid call interleaves its lists), "no result" behind them.
+// Grid (n_seg, n_queries); with n_seg > 1 the workgroup that finishes a query last merges the
+// segments' lists lk / li [n_queries][n_seg][KE] through mk / mi [n_queries][KE] (done [n_queries]:
+// zero on entry, zero again on exit).  N == 0 is allowed (no row is read).
+struct SparseArgs {
+    const int64_t* indptr; const SparsePair* pairs; int64_t N; int32_t n_terms;
+    const int64_t* q_indptr; const int32_t* q_terms; const float* q_weights; int64_t q_nnz;
+    const uint32_t* mask; int k; int KE;
+    double* lk; uint32_t* li; double* mk; uint32_t* mi; int* done;
+    unsigned long long* bad;
+    float* out_s; int64_t* out_i; double* out_k; int64_t out_ld; int64_t index_offset;
+};
+size_t sparse_search_lds_bytes(int KE, int n_seg);
+hipError_t launch_sparse_search(const SparseArgs& a, int n_queries, int n_seg, hipStream_t st);
+// The hybrid call's sets for the fuse kernel: offs [n_queries + 1] = 0, 2, 4, ... and weights
+// [2 n_queries] = (w_dense, w_sparse) per set, written on the device.
+hipError_t launch_hybrid_sets(int64_t* offs, double* weights, int n_queries, double w_dense, double w_sparse,
+                              hipStream_t st);
+
 // MaxSim search (vdb_maxsim.hip, vdb_index_search_maxsim).  Scan: sub-queries [b0, b0 + qb) of the
 // call (qb at most kRangeMaxBlock, vdb_range_plan.h) against rows [0, N), N >= 1.  A row is eligible
 // when its group id lies in [0, n_slots) and mask (optional, the row_mask layout) has its bit;

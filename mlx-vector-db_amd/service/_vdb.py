@@ -44,7 +44,8 @@ EXPORTED_SYMBOLS = (
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
     "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
-    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim",
+    "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -119,6 +120,12 @@ def load_library():
                                                ctypes.c_double, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_index_search_maxsim": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp,
                                                 c_vp, c_vp]),
+            "vdb_index_set_sparse": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
+            "vdb_index_search_sparse": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                c_i64, c_vp]),
+            "vdb_index_search_hybrid": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_double, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                c_i64, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -214,6 +221,36 @@ def pack_query_sets(sets, dim: int) -> Tuple[np.ndarray, np.ndarray]:
         np.cumsum([a.shape[0] for a in arrs], out=offs[1:])
     q = np.concatenate(arrs) if arrs else np.zeros((0, dim), np.float32)
     return np.ascontiguousarray(q, dtype=np.float32), offs
+
+
+def pack_sparse_vectors(vectors) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """A sequence of sparse vectors, each ``(indices, values)`` with the indices already strictly
+    ascending (or ``None`` / an empty pair for a vector without entries) -> the CSR triple
+    vdb_index_set_sparse and vdb_index_search_sparse take: int64 indptr [len + 1], int32 terms and
+    fp32 weights back to back.  Nothing is sorted or checked here: the library validates."""
+    ts, ws = [], []
+    for v in vectors:
+        if v is None:
+            t, w = (), ()
+        else:
+            t, w = v
+        t = np.asarray(t)
+        if t.size and t.dtype.kind not in "iu":
+            raise ValueError(f"term ids must be integers, got dtype {t.dtype}")
+        if t.size and (int(t.min()) < -2**31 or int(t.max()) >= 2**31):
+            raise ValueError("term ids must fit int32")
+        w = np.asarray(w, dtype=np.float32).reshape(-1)
+        t = t.astype(np.int32, copy=False).reshape(-1)
+        if t.size != w.size:
+            raise ValueError(f"a sparse vector needs one value per index, got {t.size} and {w.size}")
+        ts.append(t)
+        ws.append(w)
+    indptr = np.zeros(len(ts) + 1, np.int64)
+    if ts:
+        np.cumsum([t.size for t in ts], out=indptr[1:])
+    terms = np.concatenate(ts) if ts else np.zeros(0, np.int32)
+    weights = np.concatenate(ws) if ws else np.zeros(0, np.float32)
+    return indptr, np.ascontiguousarray(terms, np.int32), np.ascontiguousarray(weights, np.float32)
 
 
 def pack_row_lists(lists) -> Tuple[np.ndarray, np.ndarray]:
@@ -728,6 +765,134 @@ class NativeIndex:
             ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, ctypes.c_void_p(out_scores_ptr or None),
             ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_fused_ptr or None),
             ctypes.c_void_p(out_hits_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
+
+    # -- sparse and hybrid search ----------------------------------------------------
+    @staticmethod
+    def _csr(indptr, terms, weights, what: str):
+        ip = np.ascontiguousarray(indptr, dtype=np.int64).reshape(-1)
+        if ip.size < 1:
+            raise ValueError(f"{what} indptr needs n + 1 entries")
+        t = np.asarray(terms)
+        if t.size and t.dtype.kind not in "iu":
+            raise ValueError(f"{what} term ids must be integers, got dtype {t.dtype}")
+        if t.size and (int(t.min()) < -2**31 or int(t.max()) >= 2**31):
+            raise ValueError(f"{what} term ids must fit int32")
+        t = np.ascontiguousarray(t.reshape(-1), dtype=np.int32)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if t.size != w.size:
+            raise ValueError(f"{what} terms and weights differ in length: {t.size} and {w.size}")
+        return ip, t, w
+
+    def set_sparse(self, indptr, terms=None, weights=None, n_terms: int = 0) -> None:
+        """include/vdb.h vdb_index_set_sparse, host memory: attach one sparse vector per row in CSR
+        form (``len(indptr) == count + 1``; row r's entries are ``terms / weights[indptr[r]:
+        indptr[r + 1]]``, term ids strictly ascending in [0, ``n_terms``), weights finite).
+        ``indptr=None`` detaches the column.  Every add, remove and clear drops it; an update keeps
+        it.  A column the library refuses raises ValueError and leaves the earlier one attached."""
+        if indptr is None:
+            _check(self._lib.vdb_index_set_sparse(self._h, None, None, None, 0, 0, 0, MEM_HOST, None))
+            return
+        ip, t, w = self._csr(indptr, terms if terms is not None else (), weights if weights is not None else (), "sparse column")
+        _check(self._lib.vdb_index_set_sparse(self._h, _ptr(ip), _ptr(t) if t.size else None, _ptr(w) if w.size else None,
+                                              ip.size - 1, t.size, int(n_terms), MEM_HOST, None))
+
+    def set_sparse_device(self, indptr_ptr: int, terms_ptr: int, weights_ptr: int, n: int, nnz: int, n_terms: int,
+                          stream: int = 0) -> None:
+        """vdb_index_set_sparse with a device-memory column (int64 indptr, int32 terms, fp32 weights),
+        read after the work queued on ``stream`` and validated by a kernel."""
+        _check(self._lib.vdb_index_set_sparse(self._h, ctypes.c_void_p(indptr_ptr or None), ctypes.c_void_p(terms_ptr or None),
+                                              ctypes.c_void_p(weights_ptr or None), int(n), int(nnz), int(n_terms),
+                                              MEM_DEVICE, ctypes.c_void_p(stream or None)))
+
+    def _mask_ptr(self, row_mask):
+        if row_mask is None:
+            return None, None
+        m = np.ascontiguousarray(row_mask, dtype=np.uint32)
+        need = (self.count() + 31) // 32
+        if m.size < need:
+            raise ValueError(f"row_mask needs {need} uint32 words, got {m.size}")
+        return m, _ptr(m)
+
+    def search_sparse(self, q_indptr, q_terms, q_weights, k: int, row_mask: Optional[np.ndarray] = None,
+                      with_keys: bool = False, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_sparse, host memory: query b is the sparse vector
+        ``q_terms / q_weights[q_indptr[b]:q_indptr[b + 1]]`` (``pack_sparse_vectors`` builds the
+        triple; at most 1 024 terms, ids strictly ascending); the rows that share a term with it rank
+        by (fp64 dot product desc, row asc).  Returns (scores f32 [B,k], indices i64 [B,k][, keys f64
+        [B,k]]); slots past min(k, matching rows) are 0 / -1 / -inf.  Needs a column (``set_sparse``);
+        ``k`` outside [1, 1024] or a bad query raises ValueError."""
+        ip, t, w = self._csr(q_indptr, q_terms, q_weights, "query")
+        B, k = ip.size - 1, int(k)
+        scores = np.empty((B, max(k, 0)), dtype=np.float32)  # (a bad k is the library's to refuse)
+        idx = np.empty((B, max(k, 0)), dtype=np.int64)
+        keys = np.empty((B, max(k, 0)), dtype=np.float64) if with_keys else None
+        m, mask_p = self._mask_ptr(row_mask)
+        _check(self._lib.vdb_index_search_sparse(
+            self._h, _ptr(ip), _ptr(t) if t.size else None, _ptr(w) if w.size else None, B, t.size, k, mask_p, MEM_HOST,
+            _ptr(scores), _ptr(idx), _ptr(keys) if keys is not None else None, int(index_offset), None))
+        return (scores, idx, keys) if with_keys else (scores, idx)
+
+    def search_sparse_device(self, q_indptr_ptr: int, q_terms_ptr: int, q_weights_ptr: int, n_queries: int, q_nnz: int,
+                             k: int, out_scores_ptr: int, out_idx_ptr: int, out_keys_ptr: int = 0, mask_ptr: int = 0,
+                             index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_sparse with device-memory arguments; stream-ordered, the queries are not
+        validated on the host and nothing is read back (a bad query comes back empty and counts in stat
+        ``sparse_bad_queries``)."""
+        _check(self._lib.vdb_index_search_sparse(
+            self._h, ctypes.c_void_p(q_indptr_ptr or None), ctypes.c_void_p(q_terms_ptr or None),
+            ctypes.c_void_p(q_weights_ptr or None), int(n_queries), int(q_nnz), int(k), ctypes.c_void_p(mask_ptr or None),
+            MEM_DEVICE, ctypes.c_void_p(out_scores_ptr or None), ctypes.c_void_p(out_idx_ptr or None),
+            ctypes.c_void_p(out_keys_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
+
+    def search_hybrid(self, queries: np.ndarray, q_indptr, q_terms, q_weights, k: int, fetch_k: int,
+                      weights=(1.0, 1.0), rrf_c: float = 60.0, row_mask: Optional[np.ndarray] = None,
+                      with_fused: bool = False, with_hits: bool = False, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_hybrid, host memory: query b fuses the best ``fetch_k`` rows
+        of the dense search for ``queries[b]`` with the best ``fetch_k`` of the sparse search for
+        sparse query b by weighted reciprocal rank, ``weights = (w_dense, w_sparse)``, and ranks by
+        (fused desc, row asc).  Returns (scores f32 [B,k], indices i64 [B,k][, fused f64 [B,k]][, hits
+        i32 [B,k]]).  ``k`` / ``fetch_k`` outside 1 <= k <= fetch_k <= 200, a bad weight or a bad query
+        raises ValueError."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(-1, self.dim) if q.size == 0 else q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must have shape (n_queries, {self.dim}), got {np.shape(queries)}")
+        ip, t, w = self._csr(q_indptr, q_terms, q_weights, "query")
+        B, k = ip.size - 1, int(k)
+        if q.shape[0] != B:
+            raise ValueError(f"{q.shape[0]} dense queries but {B} sparse ones")
+        if len(weights) != 2:
+            raise ValueError("weights must be (w_dense, w_sparse)")
+        scores = np.empty((B, max(k, 0)), dtype=np.float32)
+        idx = np.empty((B, max(k, 0)), dtype=np.int64)
+        fused = np.empty((B, max(k, 0)), dtype=np.float64) if with_fused else None
+        hits = np.empty((B, max(k, 0)), dtype=np.int32) if with_hits else None
+        m, mask_p = self._mask_ptr(row_mask)
+        _check(self._lib.vdb_index_search_hybrid(
+            self._h, _ptr(q) if B else None, _ptr(ip), _ptr(t) if t.size else None, _ptr(w) if w.size else None, B, t.size,
+            k, int(fetch_k), float(weights[0]), float(weights[1]), float(rrf_c), mask_p, MEM_HOST, _ptr(scores), _ptr(idx),
+            _ptr(fused) if fused is not None else None, _ptr(hits) if hits is not None else None, int(index_offset), None))
+        out = (scores, idx)
+        if with_fused:
+            out += (fused,)
+        if with_hits:
+            out += (hits,)
+        return out
+
+    def search_hybrid_device(self, q_ptr: int, q_indptr_ptr: int, q_terms_ptr: int, q_weights_ptr: int, n_queries: int,
+                             q_nnz: int, k: int, fetch_k: int, out_scores_ptr: int, out_idx_ptr: int,
+                             weights=(1.0, 1.0), rrf_c: float = 60.0, out_fused_ptr: int = 0, out_hits_ptr: int = 0,
+                             mask_ptr: int = 0, index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_hybrid with device-memory arguments; stream-ordered, nothing is read back
+        (a bad sparse query contributes an empty sparse list and counts in ``sparse_bad_queries``)."""
+        _check(self._lib.vdb_index_search_hybrid(
+            self._h, ctypes.c_void_p(q_ptr or None), ctypes.c_void_p(q_indptr_ptr or None),
+            ctypes.c_void_p(q_terms_ptr or None), ctypes.c_void_p(q_weights_ptr or None), int(n_queries), int(q_nnz),
+            int(k), int(fetch_k), float(weights[0]), float(weights[1]), float(rrf_c), ctypes.c_void_p(mask_ptr or None),
+            MEM_DEVICE, ctypes.c_void_p(out_scores_ptr or None), ctypes.c_void_p(out_idx_ptr or None),
+            ctypes.c_void_p(out_fused_ptr or None), ctypes.c_void_p(out_hits_ptr or None), int(index_offset),
+            ctypes.c_void_p(stream or None)))
 
     # -- MaxSim search -------------------------------------------------------------
     def _maxsim_sets(self, query_sets):

@@ -69,6 +69,79 @@ FUSED_MAX_LISTS = 16
 MAXSIM_MAX_K = 128
 MAXSIM_MAX_VECTORS = 64
 MAXSIM_MAX_CELLS = 1 << 27
+# sparse_query / hybrid_query: the most rows per sparse query and the most terms a query's sparse
+# vector may hold (include/vdb.h vdb_index_search_sparse; hybrid_query's k and fetch_k follow
+# FUSED_MAX_*); POST /vectors/sparse_query and /vectors/hybrid_query answer a value outside them with 400
+SPARSE_MAX_K = 1024
+SPARSE_MAX_QUERY_TERMS = 1024
+
+
+def _sparse_pair(value, what: str):
+    """``{"indices": [...], "values": [...]}`` -> (int64 indices, fp32 values) sorted by index; a
+    repeated index, a negative or non-integer one, lengths that differ or a non-finite value raise
+    ValueError."""
+    if not isinstance(value, dict) or "indices" not in value or "values" not in value:
+        raise ValueError(f'{what} must be {{"indices": [...], "values": [...]}}')
+    idx = np.asarray(value["indices"])
+    if idx.size and idx.dtype.kind not in "iu":
+        raise ValueError(f"{what}: indices must be integers")
+    idx = idx.astype(np.int64, copy=False).reshape(-1)
+    val = np.asarray(value["values"], dtype=np.float64).reshape(-1)
+    if idx.size != val.size:
+        raise ValueError(f"{what}: {idx.size} indices but {val.size} values")
+    if idx.size and (int(idx.min()) < 0 or int(idx.max()) > 2**31 - 2):
+        raise ValueError(f"{what}: indices must be in [0, 2^31 - 2]")
+    if not (np.isfinite(val).all() and (np.abs(val) <= float(np.finfo(np.float32).max)).all()):
+        raise ValueError(f"{what}: values must be finite in fp32")
+    order = np.argsort(idx, kind="stable")
+    idx, val = idx[order], val[order]
+    if idx.size > 1 and (np.diff(idx) == 0).any():
+        raise ValueError(f"{what}: index {int(idx[1:][np.diff(idx) == 0][0])} is repeated")
+    return idx, val.astype(np.float32)
+
+
+def build_sparse_column(metadata: List[Dict], n: int, sparse_key: str = "sparse"):
+    """The CSR column ``vdb_index_set_sparse`` takes, from the first ``n`` rows' metadata: row r's
+    sparse vector is ``metadata[r][sparse_key]`` (``{"indices": [...], "values": [...]}``, sorted
+    here; a repeated index is a ValueError), a row without the key has no entry.  -> (indptr int64
+    [n + 1], terms int32, weights fp32, n_terms); n_terms is one more than the largest index seen, 0
+    when no row has an entry."""
+    ts, ws = [], []
+    indptr = np.zeros(n + 1, np.int64)
+    for r in range(n):
+        m = metadata[r] if r < len(metadata) else None
+        v = m.get(sparse_key) if isinstance(m, dict) else None
+        if v is not None:
+            t, w = _sparse_pair(v, f"row {r}: metadata[{sparse_key!r}]")
+            ts.append(t)
+            ws.append(w)
+            indptr[r + 1] = t.size
+    np.cumsum(indptr, out=indptr)
+    terms = np.concatenate(ts).astype(np.int32) if ts else np.zeros(0, np.int32)
+    weights = np.concatenate(ws).astype(np.float32) if ws else np.zeros(0, np.float32)
+    n_terms = int(terms.max()) + 1 if terms.size else 0
+    return indptr, terms, weights, n_terms
+
+
+def normalize_sparse_query(sparse):
+    """A query's sparse vector (``{"indices", "values"}``, or None for none) -> (indices, values)
+    sorted by index with the zero weights dropped; a repeated index or more than
+    SPARSE_MAX_QUERY_TERMS terms is a ValueError."""
+    if sparse is None:
+        return np.zeros(0, np.int64), np.zeros(0, np.float32)
+    idx, val = _sparse_pair(sparse, "the query's sparse vector")
+    keep = val != 0
+    idx, val = idx[keep], val[keep]
+    if idx.size > SPARSE_MAX_QUERY_TERMS:
+        raise ValueError(f"a query's sparse vector takes at most {SPARSE_MAX_QUERY_TERMS} terms, got {idx.size}")
+    return idx, val
+
+
+def clip_sparse_query(q, n_terms: int):
+    """A normalised query without the indices at or past ``n_terms``: no row can hold them."""
+    idx, val = q
+    keep = idx < n_terms
+    return idx[keep].astype(np.int32), val[keep]
 
 
 # DESIGN.md §13: half the smallest measured crossover of the row-list search against the masked
@@ -298,6 +371,12 @@ class MLXVectorStore:
         self._group_tag: Optional[Tuple] = None
         self._group_values: List[Any] = []
         self._group_sets = -1
+        # sparse_query / hybrid_query: the one sparse column attached to the index, (key, rows,
+        # update count), its n_terms and the index's "sparse_sets" when it was attached
+        self._sparse_lock = threading.Lock()
+        self._sparse_tag: Optional[Tuple] = None
+        self._sparse_terms = 0
+        self._sparse_sets = -1
         self._hnsw_index = None
         self._files = StoreFiles(self.store_path)
         self._coalescer = _QueryCoalescer(lambda Q, k, filters=None: self._search_filtered(
@@ -1069,6 +1148,147 @@ class MLXVectorStore:
                 return empty
             scores, idx, fused, hits = self._index.search_fused(Q, offs, k, fetch_k, fusion, w, c, row_mask=mask,
                                                                 with_fused=True, with_hits=True)
+            meta = self._metadata
+            out = []
+            for b in range(B):
+                valid = idx[b] >= 0
+                ib = idx[b][valid].tolist()
+                out.append((ib, scores[b][valid].astype(np.float64).tolist(),
+                            [meta[i] if i < len(meta) else {} for i in ib], fused[b][valid].tolist(),
+                            hits[b][valid].tolist()))
+            return out
+
+    # ---- sparse and hybrid query ----------------------------------------------------------
+    def _attach_sparse(self, sparse_key: str) -> int:
+        """Make the rows' sparse vectors under the metadata key ``sparse_key`` the sparse column
+        attached to the index (read lock and _sparse_lock held) -> its ``n_terms`` (0: no row has an
+        entry, nothing is searched).  Built once and kept under ``_attach_groups``' tag rule: while
+        the key, the row count and the rows' contents stay as they were and the index still holds it
+        (an add, a delete and a clear drop it; an upsert may change a row's metadata)."""
+        n = self._vector_count
+        tag = (sparse_key, n, self._index.stat("rows_updated"))
+        if self._sparse_tag == tag and self._index.stat("sparse_rows") == n \
+                and self._index.stat("sparse_sets") == self._sparse_sets:
+            return self._sparse_terms
+        indptr, terms, weights, n_terms = build_sparse_column(self._metadata, n, sparse_key)
+        self._sparse_tag = None
+        if n_terms == 0:  # no row has an entry: no other key's column stays attached
+            if self._index.stat("sparse_rows"):
+                self._index.set_sparse(None)
+        else:
+            self._index.set_sparse(indptr, terms, weights, n_terms)
+            self._sparse_tag, self._sparse_terms = tag, n_terms
+            self._sparse_sets = self._index.stat("sparse_sets")
+        return n_terms
+
+    def sparse_query(self, sparse, k: int = 10, filter_metadata: Optional[Dict] = None,
+                     sparse_key: str = "sparse") -> Tuple:
+        """The ``k`` rows whose sparse vector (metadata key ``sparse_key``: ``{"indices": [...],
+        "values": [...]}``, e.g. BM25, SPLADE or BGE-M3 term weights) has the greatest dot product
+        with ``sparse`` (the same form) -> (indices, scores, metadata), best first; only rows that
+        share a term with the query are returned, ties go to the lower row id.  Exact, in fp64, on the
+        device (include/vdb.h vdb_index_search_sparse).  The reference has no such read."""
+        return self.batch_sparse_query([sparse], k, filter_metadata, sparse_key)[0]
+
+    def batch_sparse_query(self, sparses, k: int = 10, filter_metadata: Optional[Dict] = None,
+                           sparse_key: str = "sparse") -> List[Tuple]:
+        """``sparse_query`` for a list of sparse vectors from one device call: one (indices, scores,
+        metadata) tuple per query."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("sparse query is not supported on a multi-device store")
+        k = int(k)
+        if not 1 <= k <= SPARSE_MAX_K:
+            raise ValueError(f"k must be in [1, {SPARSE_MAX_K}], got {k}")
+        qs = [normalize_sparse_query(s) for s in sparses]
+        B = len(qs)
+        empty = [([], [], []) for _ in range(B)]
+        with _Read(self._rw):
+            if self._vector_count == 0 or B == 0:
+                return empty
+            mask = self._sparse_mask(filter_metadata)
+            if mask is False:
+                return empty
+            with self._sparse_lock:  # one attached column: attach and search as one step
+                n_terms = self._attach_sparse(sparse_key)
+                if n_terms == 0:
+                    return empty
+                ip, t, w = _vdb.pack_sparse_vectors([clip_sparse_query(q, n_terms) for q in qs])
+                scores, idx = self._index.search_sparse(ip, t, w, k, row_mask=mask)
+            meta = self._metadata
+            out = []
+            for b in range(B):
+                valid = idx[b] >= 0
+                ib = idx[b][valid].tolist()
+                out.append((ib, scores[b][valid].astype(np.float64).tolist(), [meta[i] if i < len(meta) else {} for i in ib]))
+            return out
+
+    def _sparse_mask(self, filter_metadata: Optional[Dict]):
+        """The row_mask of a sparse read (read lock held, rows present): None without a filter, False
+        when nothing matches the filter (no device call is needed)."""
+        if not filter_metadata:
+            return None
+        mask, eligible = self._meta_index.bitmap(filter_metadata, self._vector_count)
+        return mask if eligible else False
+
+    def hybrid_query(self, query_vector: Union[np.ndarray, Any], sparse, k: int = 10, fetch_k: Optional[int] = None,
+                     weights=(1.0, 1.0), rrf_c: float = 60.0, filter_metadata: Optional[Dict] = None,
+                     sparse_key: str = "sparse") -> Tuple:
+        """Dense and sparse retrieval fused: the best ``fetch_k`` rows (``None``: min(200, max(k, 4
+        k))) of ``query`` for ``query_vector`` and the best ``fetch_k`` of ``sparse_query`` for
+        ``sparse`` are fused per row by weighted reciprocal rank, ``weights[0] / (rrf_c + dense rank) +
+        weights[1] / (rrf_c + sparse rank)``, -> (indices, scores, metadata, fused, hits) as
+        ``fused_query`` returns them (hits: 1 or 2).  Ties go to the lower row id.  One device call,
+        exact and the same for every precision (include/vdb.h vdb_index_search_hybrid)."""
+        q = _as_matrix(query_vector)
+        if q.ndim == 2 and q.shape[0] == 1:
+            q = q[0]
+        if q.ndim != 1:
+            raise ValueError(f"hybrid_query takes one vector of shape (dim,) or (1, dim), got {q.shape}; "
+                             "use batch_hybrid_query for several")
+        return self.batch_hybrid_query(q[None, :], [sparse], k, fetch_k, weights, rrf_c, filter_metadata, sparse_key)[0]
+
+    def batch_hybrid_query(self, query_vectors: Union[np.ndarray, Any], sparses, k: int = 10,
+                           fetch_k: Optional[int] = None, weights=(1.0, 1.0), rrf_c: float = 60.0,
+                           filter_metadata: Optional[Dict] = None, sparse_key: str = "sparse") -> List[Tuple]:
+        """``hybrid_query`` for a [B, dim] block of vectors and B sparse vectors from one device call:
+        one (indices, scores, metadata, fused, hits) tuple per query."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("hybrid query is not supported on a multi-device store")
+        k = int(k)
+        if not 1 <= k <= FUSED_MAX_K:
+            raise ValueError(f"k must be in [1, {FUSED_MAX_K}], got {k}")
+        fetch_k = min(FUSED_MAX_FETCH, max(k, 4 * k)) if fetch_k is None else int(fetch_k)
+        if not k <= fetch_k <= FUSED_MAX_FETCH:
+            raise ValueError(f"fetch_k must be in [k, {FUSED_MAX_FETCH}], got fetch_k={fetch_k} k={k}")
+        c = float(rrf_c)
+        if not 0.0 <= c < float("inf"):  # (a NaN fails both comparisons)
+            raise ValueError(f"rrf_c must be finite and >= 0, got {rrf_c}")
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != 2 or not (np.isfinite(w).all() and (w >= 0).all()):
+            raise ValueError("weights must be (w_dense, w_sparse), finite and >= 0")
+        Q = _as_matrix(query_vectors)
+        if Q.ndim == 1:
+            Q = Q[None, :]
+        if Q.ndim != 2:
+            raise ValueError(f"query_vectors must be 2-D (B, dim), got {Q.shape}")
+        qs = [normalize_sparse_query(s) for s in sparses]
+        B = Q.shape[0]
+        if len(qs) != B:
+            raise ValueError(f"{B} query vectors need {B} sparse vectors, got {len(qs)}")
+        empty = [([], [], [], [], []) for _ in range(B)]
+        with _Read(self._rw):
+            # (never the graph path, never the coalescer: one exact device call for the block)
+            mask = self._range_mask(Q, filter_metadata)  # None: no filter; False: nothing to search
+            if mask is False or B == 0:
+                return empty
+            with self._sparse_lock:  # one attached column: attach and search as one step
+                n_terms = self._attach_sparse(sparse_key)
+                if n_terms == 0:  # no row has a sparse entry: an empty column of one term, every sparse list empty
+                    self._index.set_sparse(np.zeros(self._vector_count + 1, np.int64), None, None, 1)
+                    n_terms = 1
+                ip, t, sw = _vdb.pack_sparse_vectors([clip_sparse_query(q, n_terms) for q in qs])
+                scores, idx, fused, hits = self._index.search_hybrid(Q, ip, t, sw, k, fetch_k, (float(w[0]), float(w[1])),
+                                                                     c, row_mask=mask, with_fused=True, with_hits=True)
             meta = self._metadata
             out = []
             for b in range(B):
