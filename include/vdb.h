@@ -158,7 +158,9 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "maxsim_sets", "maxsim_bad_sets", "maxsim_skipped_rows") and "sparse_wgs" (workgroups per query
  * of vdb_index_search_sparse, 0 = auto; the sparse and hybrid calls' stats "sparse_rows",
  * "sparse_nnz", "sparse_sets", "sparse_searches", "sparse_queries", "sparse_bad_queries",
- * "hybrid_searches", "hybrid_queries" are described there).  Stats also: "searches", "queries",
+ * "hybrid_searches", "hybrid_queries" are described there) and "hybrid_sum_wgs" (workgroups per
+ * query of vdb_index_search_hybrid_sum, 0 = auto, 1..512; its stats "hybrid_sum_searches",
+ * "hybrid_sum_queries" are described there).  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -648,6 +650,66 @@ int32_t vdb_index_search_hybrid(vdb_index* idx, const float* queries,
                                 const uint32_t* row_mask, int32_t mem,
                                 float* out_scores, int64_t* out_indices, double* out_fused, int32_t* out_hits,
                                 int64_t index_offset, void* stream);
+
+/* --- Weighted-sum hybrid search: exact top-k of dense plus sparse scores -------------
+ * Replaces: nothing the reference has.  Beside reciprocal-rank fusion, the systems
+ * vdb_index_search_hybrid was modelled on offer a weighted sum of the two scores (Pinecone's
+ * sparse-dense alpha, Milvus' WeightedRanker, Elasticsearch's linear retriever, Weaviate's score
+ * fusion).  They add the scores of two fetched lists, where a row missing from one list counts 0
+ * there: a row that stands 250th in both rankings can have the best sum and stands in neither list.
+ * This call computes the sum for every row of the corpus and returns its exact top k.
+ *
+ *   queries      [n_queries, dim] fp32: the dense query vectors
+ *   q_indptr     [n_queries + 1] int64, q_terms / q_weights [q_nnz]: the sparse queries in CSR form,
+ *                as vdb_index_search_sparse takes them; q_nnz a host scalar
+ *   k            1..1024; n_queries at most 65 535
+ *   w_dense, w_sparse  finite, >= 0 and <= 2^64 (the cap keeps every product finite: |kd| and |ks|
+ *                are below 2^280 for any finite fp32 input, so no sum is inf - inf)
+ *   out_scores   [n_queries, k] fp32; out_indices [n_queries, k] int64; out_fused, out_dense,
+ *                out_sparse NULL or [n_queries, k] fp64
+ *   row_mask, mem, index_offset, stream: as vdb_index_search_hybrid; all pointers of one memory kind.
+ * Contract (every operation a separate fp64 operation).  For query b and row r: kd = the canonical
+ * fp64 key vdb_index_search ranks by (the cosine similarity, or minus the squared L2 distance; it
+ * stays in key units, as MMR's and MaxSim's do); ks = the key vdb_index_search_sparse's contract
+ * defines (acc = 0.0, then over the row's entries in stored order acc = acc + (double)w_e * qd[t_e]):
+ * +0.0 for a row that shares no term with the query, and never -0.0.  t1 = w_dense * kd; t2 =
+ * w_sparse * ks; u = t1 + t2; c = u + 0.0 (the last add turns -0.0 into +0.0, as MaxSim's, so equal
+ * values have equal bits).  Candidates: EVERY row below count whose mask bit is set, whether it
+ * shares a term with the query or not (unlike vdb_index_search_sparse, on purpose: an unmatched row
+ * still has its dense score).  Ranking by (c desc, row asc); the first min(k, candidates) slots hold
+ * out_indices = row + index_offset, out_fused = c, out_scores = (float)c (round to nearest even),
+ * out_dense = kd, out_sparse = ks.  Slots past that hold index -1 / score 0 / fused, dense and sparse
+ * -inf.
+ * Consequences: with w_dense == 1 and w_sparse == 0 the indices are those of vdb_index_search(k,
+ * row_mask) in its order and out_fused has the bits of its out_keys + 0.0.  A query without terms
+ * ranks by its dense key alone; that is no error.  With w_dense == 0 and w_sparse == 1 the leading
+ * slots whose out_sparse is > 0 are the leading slots of vdb_index_search_sparse(k) with keys > 0:
+ * same rows, same order, out_fused == its out_keys.  The result of a query depends only on that
+ * query.  The result is the same bytes for every precision setting and both memory kinds: only the
+ * fp32 rows, their canonical norms and the sparse column are read.
+ * Errors, before anything is launched, both memory kinds, all VDB_ERR_INVALID: those of
+ * vdb_index_search_sparse's call checks (no sparse column attached, k outside [1, 1024], n_queries or
+ * q_nnz < 0, a NULL q_indptr / out_scores / out_indices with n_queries > 0, a bad mem), a NULL
+ * queries with n_queries > 0, a weight outside [0, 2^64] or NaN, n_queries above 65 535.
+ * Host-memory calls also: the sparse queries are checked as vdb_index_search_sparse checks them, and
+ * a NaN or Inf in a dense query -> VDB_ERR_NONFINITE; no stat moves on an error.  Device-memory calls
+ * are stream-ordered and read nothing back: sparse offsets are clamped to [0, q_nnz] as the sparse
+ * kernel clamps them; a query it finds bad by vdb_index_search_sparse's rule gets "no result" in
+ * every slot and is counted in "sparse_bad_queries", its neighbours unaffected; a non-finite dense
+ * query is the caller's error, as for vdb_index_search_rows (nothing out of bounds is read).
+ * n_queries == 0 is VDB_OK; an empty index with an empty column attached gives "no result"
+ * everywhere.  Takes the shared lock and a per-search workspace, with one pinned staging copy each
+ * way for host calls, as vdb_index_search_sparse does.  Knob "hybrid_sum_wgs": workgroups per query,
+ * 0 = auto, 1..512 (results identical).  Stats: "hybrid_sum_searches", "hybrid_sum_queries"
+ * (cumulative over successful calls); "searches", "queries" and every "searches_*" stat stay still. */
+int32_t vdb_index_search_hybrid_sum(vdb_index* idx, const float* queries,
+                                    const int64_t* q_indptr, const int32_t* q_terms, const float* q_weights,
+                                    int32_t n_queries, int64_t q_nnz, int32_t k,
+                                    double w_dense, double w_sparse,
+                                    const uint32_t* row_mask, int32_t mem,
+                                    float* out_scores, int64_t* out_indices, double* out_fused,
+                                    double* out_dense, double* out_sparse,
+                                    int64_t index_offset, void* stream);
 
 /* --- MaxSim search: groups ranked by the summed best match per query vector ---------
  * Replaces: nothing the reference has.  Multi-vector ("late interaction") retrieval -- ColBERT /

@@ -134,6 +134,22 @@ class VectorHybridQuery(BaseModel):
     sparse_key: str = Field(default="sparse", description="Metadata key holding each row's sparse vector")
 
 
+class VectorHybridSumQuery(BaseModel):
+    """Dense and sparse retrieval combined by a weighted sum of the two scores: every row is ranked by
+    ``weights[0] * dense + weights[1] * sparse`` (the row's exact dense key for ``query`` and the dot
+    product of its sparse vector with ``sparse``, 0 for a row that shares no term), exactly over the
+    whole store.  Pinecone's ``alpha`` is ``weights = [alpha, 1 - alpha]``.  The store checks the
+    limits (k at most 1024, two weights in [0, 2^64]); a value outside them is a 400."""
+    user_id: str
+    model_id: str
+    query: List[float] = Field(..., description="The dense query vector")
+    sparse: SparseVector = Field(..., description="The query's sparse vector")
+    k: int = Field(default=10, description="Rows returned")
+    weights: List[float] = Field(default=[1.0, 1.0], description="(dense weight, sparse weight)")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    sparse_key: str = Field(default="sparse", description="Metadata key holding each row's sparse vector")
+
+
 class VectorMaxSimQuery(BaseModel):
     """Late-interaction ("MaxSim") retrieval: the ``k`` best values of the metadata key ``group_by``
     (documents of a multi-vector corpus) for a set of query vectors (token embeddings).  A group's
@@ -259,6 +275,14 @@ class VectorSparseQueryResponse(BaseModel):
 
 class VectorHybridQueryResponse(BaseModel):
     # best first: {"metadata", "fused_score", "hits" (1 or 2: the retrievers that returned the row), "rank"}
+    results: List[Dict[str, Any]]
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorHybridSumQueryResponse(BaseModel):
+    # best first: {"metadata", "score" (the weighted sum), "dense_score" (the store's ranking key: the
+    # cosine similarity, or minus the squared distance for euclidean), "sparse_score" (the dot product), "rank"}
     results: List[Dict[str, Any]]
     query_time_ms: float
     total_vectors_searched: int
@@ -626,6 +650,36 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in hybrid query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Hybrid query failed: {e}")
+
+    @router.post("/hybrid_sum_query", response_model=VectorHybridSumQueryResponse)
+    async def hybrid_sum_query_vectors(request: VectorHybridSumQuery, api_key: str = Depends(auth)):
+        """Dense and sparse retrieval combined by a weighted sum of the two scores, best first.  A bad
+        request (no vector, k / weights outside their limits, a bad sparse vector, dimension mismatch:
+        the store's ValueError) is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if not request.query:
+                raise HTTPException(status_code=400, detail="Query vector required")
+            sparse = {"indices": request.sparse.indices, "values": request.sparse.values}
+            loop = asyncio.get_running_loop()
+            indices, scores, metas, dense, sparse_scores = await loop.run_in_executor(
+                mgr._executor, lambda: store.hybrid_sum_query(request.query, sparse, k=request.k, weights=request.weights,
+                                                              filter_metadata=request.filter_metadata,
+                                                              sparse_key=request.sparse_key))
+            results = [{"metadata": m, "score": c, "dense_score": d, "sparse_score": p, "rank": i + 1}
+                       for i, (m, c, d, p) in enumerate(zip(metas, scores, dense, sparse_scores))]
+            return VectorHybridSumQueryResponse(results=results, query_time_ms=(time.time() - t0) * 1000,
+                                                total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Hybrid sum query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Hybrid sum query failed: {e}")
+        except Exception as e:
+            logger.error("Error in hybrid sum query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Hybrid sum query failed: {e}")
 
     @router.post("/maxsim_query", response_model=VectorMaxSimQueryResponse)
     async def maxsim_query_vectors(request: VectorMaxSimQuery, api_key: str = Depends(auth)):

@@ -31,6 +31,7 @@
 #include "vdb_fuse_plan.h"
 #include "vdb_maxsim_plan.h"
 #include "vdb_sparse_plan.h"
+#include "vdb_hybsum_plan.h"
 #include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
 #include "vdb_internal.h"
@@ -284,6 +285,9 @@ struct vdb_index {
     // kernel found bad are counted on the device (d_xmax + kSparseBadWord)
     std::atomic<int64_t> n_sparse_sets{0}, n_sparse_searches{0}, n_sparse_queries{0};
     std::atomic<int64_t> n_hybrid_searches{0}, n_hybrid_queries{0};
+    // vdb_index_search_hybrid_sum: calls and queries (successful calls)
+    std::atomic<int64_t> n_hybsum_searches{0}, n_hybsum_queries{0};
+    int64_t hybsum_wgs = 0;  // knob: workgroups per query of a weighted-sum hybrid search (0 = auto)
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
     unsigned long long* d_totals = nullptr;  // device: flagged / overflowed / flagged-in-bf16 queries of device-gated searches
@@ -1091,6 +1095,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "sparse_wgs must be in [0, %d] (0 = auto)", kSparseMaxSeg);
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->sparse_wgs = value;
+    } else if (n == "hybrid_sum_wgs") {
+        if (value < 0 || value > kHybsumMaxSeg)
+            return set_error(VDB_ERR_INVALID, "hybrid_sum_wgs must be in [0, %d] (0 = auto)", kHybsumMaxSeg);
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->hybsum_wgs = value;
     } else if (n == "group_fetch") {
         if (value < 0 || value > kGroupMaxFetch)
             return set_error(VDB_ERR_INVALID, "group_fetch must be in [0, %d] (0 = auto)", kGroupMaxFetch);
@@ -1242,6 +1251,8 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "sparse_queries") *value = ix->n_sparse_queries.load();
     else if (n == "hybrid_searches") *value = ix->n_hybrid_searches.load();
     else if (n == "hybrid_queries") *value = ix->n_hybrid_queries.load();
+    else if (n == "hybrid_sum_searches") *value = ix->n_hybsum_searches.load();
+    else if (n == "hybrid_sum_queries") *value = ix->n_hybsum_queries.load();
     else if (n == "sparse_bad_queries") {  // counted by the sparse kernel: after the searches queued so far
         HIP_TRY(hipSetDevice(ix->device));
         const int wr = wait_idle(ix);
@@ -3525,6 +3536,135 @@ int32_t vdb_index_search_hybrid(vdb_index* ix, const float* queries, const int64
     }
     ix->n_hybrid_searches++;
     ix->n_hybrid_queries += B;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_hybrid_sum(vdb_index* ix, const float* queries, const int64_t* q_indptr, const int32_t* q_terms,
+                                    const float* q_weights, int32_t B, int64_t q_nnz, int32_t k, double w_dense,
+                                    double w_sparse, const uint32_t* row_mask, int32_t mem, float* out_scores,
+                                    int64_t* out_indices, double* out_fused, double* out_dense, double* out_sparse,
+                                    int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // everything checked before any launch (a device-memory call's queries: by the kernel)
+    const bool column = ix->sparse_set && ix->sparse_n == N;
+    switch (hybsum_validate_call(B, q_nnz, k, w_dense, w_sparse, queries != nullptr, q_indptr != nullptr,
+                                 q_terms != nullptr, q_weights != nullptr, out_scores != nullptr, out_indices != nullptr,
+                                 mem, column)) {
+        case kHybsumOk: break;
+        case kHybsumBadCounts: return set_error(VDB_ERR_INVALID, "n_queries and q_nnz must be >= 0");
+        case kHybsumBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", kHybsumMaxK, k);
+        case kHybsumBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind");
+        case kHybsumNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/output pointer");
+        case kHybsumNoColumn: return set_error(VDB_ERR_INVALID, "no sparse column is attached (vdb_index_set_sparse)");
+        case kHybsumTooManyQueries:
+            return set_error(VDB_ERR_INVALID, "n_queries must be at most %d, got %d", kHybsumMaxQueries, B);
+        default: return set_error(VDB_ERR_INVALID, "w_dense and w_sparse must be in [0, 2^64]");
+    }
+    if (B == 0) return VDB_OK;
+    const int D = ix->dim;
+    const bool host = mem == VDB_MEM_HOST;
+    if (host) {
+        int64_t at = 0;
+        const int cause = sparse_validate_queries(q_indptr, q_terms, q_weights, B, q_nnz, ix->sparse_terms, &at);
+        if (cause) return sparse_call_error(cause, k, 0, at);
+        if (!all_finite(queries, (int64_t)B * D)) return set_error(VDB_ERR_NONFINITE, "query contains NaN or Inf");
+    }
+    // as vdb_index_search_sparse: the caller's stream (device memory: NULL = the null stream), or for
+    // a host-memory call without one the stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const bool parts = out_dense != nullptr || out_sparse != nullptr;
+    const int KE = sparse_ke(k);
+    const int n_seg = N > 0 ? hybsum_n_seg(ix->hybsum_wgs, N, B, ix->n_cu) : 1;
+    const HybsumScratch sc = hybsum_scratch(B, D, k, n_seg, q_nnz, N, host, masked, out_fused != nullptr,
+                                            out_dense != nullptr, out_sparse != nullptr);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    HybsumArgs a{};
+    a.Q = queries;
+    a.q_indptr = q_indptr;
+    a.q_terms = q_terms;
+    a.q_weights = q_weights;
+    a.mask = masked ? row_mask : nullptr;
+    a.out_s = out_scores;
+    a.out_i = out_indices;
+    a.out_f = out_fused;
+    a.out_d = out_dense;
+    a.out_p = out_sparse;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * D * 4);
+            std::memcpy(h + (sc.indptr - sc.in0), q_indptr, ((size_t)B + 1) * 8);
+            if (q_nnz > 0) {
+                std::memcpy(h + (sc.terms - sc.in0), q_terms, (size_t)q_nnz * 4);
+                std::memcpy(h + (sc.weights - sc.in0), q_weights, (size_t)q_nnz * 4);
+            }
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+        });
+        if (rc) return rc;
+        a.Q = reinterpret_cast<const float*>(dev + sc.q);
+        a.q_indptr = reinterpret_cast<const int64_t*>(dev + sc.indptr);
+        a.q_terms = reinterpret_cast<const int32_t*>(dev + sc.terms);
+        a.q_weights = reinterpret_cast<const float*>(dev + sc.weights);
+        a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.out_s = reinterpret_cast<float*>(dev + sc.out_s);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_f = out_fused ? reinterpret_cast<double*>(dev + sc.out_f) : nullptr;
+        a.out_d = out_dense ? reinterpret_cast<double*>(dev + sc.out_d) : nullptr;
+        a.out_p = out_sparse ? reinterpret_cast<double*>(dev + sc.out_p) : nullptr;
+    }
+    a.out_r = parts ? reinterpret_cast<uint32_t*>(dev + sc.rows) : nullptr;
+    a.done = reinterpret_cast<int*>(dev + sc.done);
+    double* qn64 = reinterpret_cast<double*>(dev + sc.qn64);
+    if (N > 0) {
+        // the canonical query norms and the zeroed per-query counters, nothing else: no query tiles
+        // (the launch the row-list search uses)
+        HIP_TRY(launch_prep_queries(a.Q, B, B, D, ix->G, ix->metric, nullptr, nullptr, qn64, nullptr, nullptr, nullptr,
+                                    nullptr, a.done, st));
+    }
+    a.qn64 = qn64;
+    a.X = ix->X;
+    a.G = ix->G;
+    a.D = D;
+    a.nrm64 = ix->nrm64;
+    a.indptr = ix->sparse_indptr;
+    a.pairs = ix->sparse_pairs;
+    a.N = N;
+    a.n_terms = ix->sparse_terms;
+    a.q_nnz = q_nnz;
+    a.w_dense = w_dense;
+    a.w_sparse = w_sparse;
+    a.k = k;
+    a.KE = KE;
+    a.lk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.lk) : nullptr;
+    a.li = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.li) : nullptr;
+    a.mk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.mk) : nullptr;
+    a.mi = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.mi) : nullptr;
+    a.bad = ix->d_xmax + kSparseBadWord;
+    a.index_offset = index_offset;
+    // (an empty index: no row is read, every slot "no result"; a device call's bad queries still count)
+    HIP_TRY(launch_hybsum_search(ix->metric, a, B, n_seg, st));
+    if (parts) HIP_TRY(launch_hybsum_parts(ix->metric, a, B, st));
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_scores, r + (sc.out_s - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+        if (out_fused) std::memcpy(out_fused, r + (sc.out_f - sc.out0), (size_t)B * k * 8);
+        if (out_dense) std::memcpy(out_dense, r + (sc.out_d - sc.out0), (size_t)B * k * 8);
+        if (out_sparse) std::memcpy(out_sparse, r + (sc.out_p - sc.out0), (size_t)B * k * 8);
+    }
+    ix->n_hybsum_searches++;
+    ix->n_hybsum_queries += B;
     return VDB_OK;
 }
 

@@ -457,6 +457,32 @@ hipError_t launch_sparse_search(const SparseArgs& a, int n_queries, int n_seg, h
 hipError_t launch_hybrid_sets(int64_t* offs, double* weights, int n_queries, double w_dense, double w_sparse,
                               hipStream_t st);
 
+// Weighted-sum hybrid search (vdb_hybsum.hip, vdb_index_search_hybrid_sum).  Query b is the dense
+// vector Q[b] (qn64[b]: its canonical norm) and the sparse entries [q_indptr[b], q_indptr[b + 1]) of
+// q_terms / q_weights, in device memory, read under the clamp and the checks of vdb_sparse_plan.h
+// whatever they hold (*bad += the queries found bad).  Row r < N is a candidate when mask (optional,
+// the row_mask layout) has its bit; its value is hybsum_combine(w_dense, kd, w_sparse, ks)
+// (vdb_hybsum_plan.h), and the best k by (value desc, row asc) go to out_s / out_i / out_f [b][k]
+// (out_f optional), "no result" behind them; out_r [b][k] (optional) gets each slot's local row,
+// 0xFFFFFFFF = none.  Grid (n_seg, n_queries); with n_seg > 1 the workgroup that finishes a query
+// last merges the segments' lists lk / li [n_queries][n_seg][KE] through mk / mi [n_queries][KE] (done
+// [n_queries]: zero on entry, zero again on exit).  N == 0 is allowed (no row is read).  Parts: one
+// wave per slot reads out_r and writes the row's kd to out_d and ks to out_p (each optional), -inf
+// for an empty slot.
+struct HybsumArgs {
+    const float* Q; const double* qn64; const float* X; int G; int D; const double* nrm64;
+    const int64_t* indptr; const SparsePair* pairs; int64_t N; int32_t n_terms;
+    const int64_t* q_indptr; const int32_t* q_terms; const float* q_weights; int64_t q_nnz;
+    double w_dense; double w_sparse;
+    const uint32_t* mask; int k; int KE;
+    double* lk; uint32_t* li; double* mk; uint32_t* mi; int* done;
+    unsigned long long* bad;
+    float* out_s; int64_t* out_i; double* out_f; uint32_t* out_r; double* out_d; double* out_p; int64_t index_offset;
+};
+size_t hybsum_search_lds_bytes(int KE, int n_seg);
+hipError_t launch_hybsum_search(int metric, const HybsumArgs& a, int n_queries, int n_seg, hipStream_t st);
+hipError_t launch_hybsum_parts(int metric, const HybsumArgs& a, int n_queries, hipStream_t st);
+
 // MaxSim search (vdb_maxsim.hip, vdb_index_search_maxsim).  Scan: sub-queries [b0, b0 + qb) of the
 // call (qb at most kRangeMaxBlock, vdb_range_plan.h) against rows [0, N), N >= 1.  A row is eligible
 // when its group id lies in [0, n_slots) and mask (optional, the row_mask layout) has its bit;

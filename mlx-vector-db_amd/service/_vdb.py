@@ -35,6 +35,8 @@ MEM_DEVICE = 1
 GRAPH_EF_MAX = 256
 # how vdb_index_search_fused combines a set's lists (include/vdb.h VDB_FUSE_*)
 FUSION_IDS = {"rrf": 0, "max": 1}
+# largest k vdb_index_search_hybrid_sum accepts (csrc/vdb_hybsum_plan.h kHybsumMaxK)
+HYBRID_SUM_MAX_K = 1024
 
 # Every symbol include/vdb.h declares (tests/test_abi.py checks the .so exports them).
 EXPORTED_SYMBOLS = (
@@ -45,7 +47,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_get_vectors",
     "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
     "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim",
-    "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_index_search_hybrid_sum", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -126,6 +128,9 @@ def load_library():
             "vdb_index_search_hybrid": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_double, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                                 c_i64, c_vp]),
+            "vdb_index_search_hybrid_sum": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, ctypes.c_double,
+                                                    ctypes.c_double, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                                    c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -893,6 +898,61 @@ class NativeIndex:
             MEM_DEVICE, ctypes.c_void_p(out_scores_ptr or None), ctypes.c_void_p(out_idx_ptr or None),
             ctypes.c_void_p(out_fused_ptr or None), ctypes.c_void_p(out_hits_ptr or None), int(index_offset),
             ctypes.c_void_p(stream or None)))
+
+    def search_hybrid_sum(self, queries: np.ndarray, q_indptr, q_terms, q_weights, k: int, weights=(1.0, 1.0),
+                          row_mask: Optional[np.ndarray] = None, with_fused: bool = False, with_parts: bool = False,
+                          index_offset: int = 0):
+        """include/vdb.h vdb_index_search_hybrid_sum, host memory: every row whose mask bit is set is
+        ranked by ``(w_dense * kd + w_sparse * ks) + 0.0`` in fp64, ``kd`` the dense key of
+        ``queries[b]`` (cosine similarity, or minus the squared distance) and ``ks`` the sparse dot
+        product with sparse query b, ``weights = (w_dense, w_sparse)`` each in [0, 2^64]; the exact top
+        ``k`` of the whole corpus by (value desc, row asc).  Returns (scores f32 [B,k], indices i64
+        [B,k][, fused f64 [B,k]][, dense f64 [B,k], sparse f64 [B,k]]); slots past min(k, eligible rows)
+        are 0 / -1 / -inf.  ``k`` outside [1, 1024], a bad weight or a bad query raises ValueError."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(-1, self.dim) if q.size == 0 else q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must have shape (n_queries, {self.dim}), got {np.shape(queries)}")
+        ip, t, w = self._csr(q_indptr, q_terms, q_weights, "query")
+        B, k = ip.size - 1, int(k)
+        if q.shape[0] != B:
+            raise ValueError(f"{q.shape[0]} dense queries but {B} sparse ones")
+        if len(weights) != 2:
+            raise ValueError("weights must be (w_dense, w_sparse)")
+        shape = (B, max(k, 0))  # (a bad k is the library's to refuse)
+        scores = np.empty(shape, dtype=np.float32)
+        idx = np.empty(shape, dtype=np.int64)
+        fused = np.empty(shape, dtype=np.float64) if with_fused else None
+        dense = np.empty(shape, dtype=np.float64) if with_parts else None
+        sparse = np.empty(shape, dtype=np.float64) if with_parts else None
+        m, mask_p = self._mask_ptr(row_mask)
+        _check(self._lib.vdb_index_search_hybrid_sum(
+            self._h, _ptr(q) if B else None, _ptr(ip), _ptr(t) if t.size else None, _ptr(w) if w.size else None, B, t.size,
+            k, float(weights[0]), float(weights[1]), mask_p, MEM_HOST, _ptr(scores), _ptr(idx),
+            _ptr(fused) if fused is not None else None, _ptr(dense) if dense is not None else None,
+            _ptr(sparse) if sparse is not None else None, int(index_offset), None))
+        out = (scores, idx)
+        if with_fused:
+            out += (fused,)
+        if with_parts:
+            out += (dense, sparse)
+        return out
+
+    def search_hybrid_sum_device(self, q_ptr: int, q_indptr_ptr: int, q_terms_ptr: int, q_weights_ptr: int,
+                                 n_queries: int, q_nnz: int, k: int, out_scores_ptr: int, out_idx_ptr: int,
+                                 weights=(1.0, 1.0), out_fused_ptr: int = 0, out_dense_ptr: int = 0,
+                                 out_sparse_ptr: int = 0, mask_ptr: int = 0, index_offset: int = 0,
+                                 stream: int = 0) -> None:
+        """vdb_index_search_hybrid_sum with device-memory arguments; stream-ordered, nothing is read
+        back (a bad sparse query comes back empty and counts in stat ``sparse_bad_queries``)."""
+        _check(self._lib.vdb_index_search_hybrid_sum(
+            self._h, ctypes.c_void_p(q_ptr or None), ctypes.c_void_p(q_indptr_ptr or None),
+            ctypes.c_void_p(q_terms_ptr or None), ctypes.c_void_p(q_weights_ptr or None), int(n_queries), int(q_nnz),
+            int(k), float(weights[0]), float(weights[1]), ctypes.c_void_p(mask_ptr or None), MEM_DEVICE,
+            ctypes.c_void_p(out_scores_ptr or None), ctypes.c_void_p(out_idx_ptr or None),
+            ctypes.c_void_p(out_fused_ptr or None), ctypes.c_void_p(out_dense_ptr or None),
+            ctypes.c_void_p(out_sparse_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
 
     # -- MaxSim search -------------------------------------------------------------
     def _maxsim_sets(self, query_sets):

@@ -74,6 +74,12 @@ MAXSIM_MAX_CELLS = 1 << 27
 # FUSED_MAX_*); POST /vectors/sparse_query and /vectors/hybrid_query answer a value outside them with 400
 SPARSE_MAX_K = 1024
 SPARSE_MAX_QUERY_TERMS = 1024
+# hybrid_sum_query: the most rows per query, the most queries of one call and the greatest weight
+# (include/vdb.h vdb_index_search_hybrid_sum); POST /vectors/hybrid_sum_query answers a value outside
+# them with 400
+HYBRID_SUM_MAX_K = _vdb.HYBRID_SUM_MAX_K
+HYBRID_SUM_MAX_QUERIES = 65535
+HYBRID_SUM_MAX_WEIGHT = 2.0 ** 64
 
 
 def _sparse_pair(value, what: str):
@@ -1297,6 +1303,76 @@ class MLXVectorStore:
                 out.append((ib, scores[b][valid].astype(np.float64).tolist(),
                             [meta[i] if i < len(meta) else {} for i in ib], fused[b][valid].tolist(),
                             hits[b][valid].tolist()))
+            return out
+
+    def hybrid_sum_query(self, query_vector: Union[np.ndarray, Any], sparse, k: int = 10, weights=(1.0, 1.0),
+                         filter_metadata: Optional[Dict] = None, sparse_key: str = "sparse") -> Tuple:
+        """Dense and sparse retrieval combined by a weighted sum of the two SCORES: every row is ranked
+        by ``weights[0] * dense + weights[1] * sparse``, ``dense`` its exact key for ``query_vector``
+        (the cosine similarity; minus the SQUARED distance for euclidean) and ``sparse`` the dot product
+        of its sparse vector (metadata key ``sparse_key``) with ``sparse``, 0 for a row that shares no
+        term -> (indices, scores, metadata, dense, sparse), best first; ties go to the lower row id.
+        Unlike ``hybrid_query`` (reciprocal rank of two fetched lists) the score magnitudes count and
+        nothing is fetched first: the sum is formed for every row of the store, in fp64, so a row that
+        is far down both rankings and still has the best sum is found.  Every row is a candidate,
+        whether it shares a term or not.  Pinecone's sparse-dense ``alpha`` is ``weights=(alpha, 1 -
+        alpha)``; Milvus' WeightedRanker and Elasticsearch's linear retriever are the same sum.  The
+        weights lie in [0, 2^64]; scores are not normalised.  One device call, exact and the same for
+        every precision (include/vdb.h vdb_index_search_hybrid_sum).  The reference has no such
+        read."""
+        q = _as_matrix(query_vector)
+        if q.ndim == 2 and q.shape[0] == 1:
+            q = q[0]
+        if q.ndim != 1:
+            raise ValueError(f"hybrid_sum_query takes one vector of shape (dim,) or (1, dim), got {q.shape}; "
+                             "use batch_hybrid_sum_query for several")
+        return self.batch_hybrid_sum_query(q[None, :], [sparse], k, weights, filter_metadata, sparse_key)[0]
+
+    def batch_hybrid_sum_query(self, query_vectors: Union[np.ndarray, Any], sparses, k: int = 10, weights=(1.0, 1.0),
+                               filter_metadata: Optional[Dict] = None, sparse_key: str = "sparse") -> List[Tuple]:
+        """``hybrid_sum_query`` for a [B, dim] block of vectors and B sparse vectors from one device
+        call: one (indices, scores, metadata, dense, sparse) tuple per query."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("hybrid sum query is not supported on a multi-device store")
+        k = int(k)
+        if not 1 <= k <= HYBRID_SUM_MAX_K:
+            raise ValueError(f"k must be in [1, {HYBRID_SUM_MAX_K}], got {k}")
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != 2 or not ((w >= 0).all() and (w <= HYBRID_SUM_MAX_WEIGHT).all()):  # (a NaN fails both)
+            raise ValueError("weights must be (w_dense, w_sparse), each in [0, 2^64]")
+        Q = _as_matrix(query_vectors)
+        if Q.ndim == 1:
+            Q = Q[None, :]
+        if Q.ndim != 2:
+            raise ValueError(f"query_vectors must be 2-D (B, dim), got {Q.shape}")
+        qs = [normalize_sparse_query(s) for s in sparses]
+        B = Q.shape[0]
+        if len(qs) != B:
+            raise ValueError(f"{B} query vectors need {B} sparse vectors, got {len(qs)}")
+        if B > HYBRID_SUM_MAX_QUERIES:
+            raise ValueError(f"at most {HYBRID_SUM_MAX_QUERIES} queries per call, got {B}")
+        empty = [([], [], [], [], []) for _ in range(B)]
+        with _Read(self._rw):
+            # (never the graph path, never the coalescer: one exact device call for the block)
+            mask = self._range_mask(Q, filter_metadata)  # None: no filter; False: nothing to search
+            if mask is False or B == 0:
+                return empty
+            with self._sparse_lock:  # one attached column: attach and search as one step
+                n_terms = self._attach_sparse(sparse_key)
+                if n_terms == 0:  # no row has a sparse entry: an empty column of one term, every sparse key 0
+                    self._index.set_sparse(np.zeros(self._vector_count + 1, np.int64), None, None, 1)
+                    n_terms = 1
+                ip, t, sw = _vdb.pack_sparse_vectors([clip_sparse_query(q, n_terms) for q in qs])
+                scores, idx, dense, sparse = self._index.search_hybrid_sum(Q, ip, t, sw, k, (float(w[0]), float(w[1])),
+                                                                           row_mask=mask, with_parts=True)
+            meta = self._metadata
+            out = []
+            for b in range(B):
+                valid = idx[b] >= 0
+                ib = idx[b][valid].tolist()
+                out.append((ib, scores[b][valid].astype(np.float64).tolist(),
+                            [meta[i] if i < len(meta) else {} for i in ib], dense[b][valid].tolist(),
+                            sparse[b][valid].tolist()))
             return out
 
     # ---- MaxSim query ------------------------------------------------------------------
