@@ -25,35 +25,53 @@ import numpy as np
 from oracle import ref_cpu
 
 
-def i8_model(V, Q, metric, prec, want_approx=True):
-    """(approx [N, B], eps [B], shift [B]) of the int8 pass (vdb_scan8_kernel.h, vdb_scan8.hip
-    prep8, vdb_api.cpp fa.*), prec "i8" or "i8x3".  want_approx=False skips the integer matmuls
-    (approx is None): eps and shift only."""
-    f32 = np.float32
-    D = V.shape[1]
+def _scored_rows(V, metric):
+    """(Y, nr): the rows a pass scores (cosine: normalised in fp32 as pack_rows does) and the fp64
+    row norms."""
     nr = np.sqrt((V.astype(np.float64) ** 2).sum(1))
     if metric == "cosine":
-        iv = (1.0 / np.maximum(nr, 1e-8)).astype(f32)
-        Y = (V * iv[:, None]).astype(f32)
+        iv = (1.0 / np.maximum(nr, 1e-8)).astype(np.float32)
+        return (V * iv[:, None]).astype(np.float32), nr
+    return V.astype(np.float32), nr
+
+
+def i8_model(V, Q, metric, prec, want_approx=True, setup=None, maxima=None):
+    """(approx [N, B], eps [B], shift [B]) of the int8 pass (vdb_scan8_kernel.h, vdb_scan8.hip
+    prep8, vdb_api.cpp fa.*), prec "i8", "i8x3" or "i8q".  want_approx=False skips the integer
+    matmuls (approx is None): eps and shift only.
+
+    setup: the rows [m, D] (m <= 65536) that mu, s_x and dir are derived from, where they are not
+    the first min(N, 65536) rows of V (vdb_api.cpp vdb_index_add: an add that does not double the
+    index keeps the earlier setup; vdb_index_update and vdb_index_remove never derive it again).
+    maxima: the rows of V (index array or boolean mask) whose residuals, plane norms and norms
+    enter the running maxima eps is built from; default all of them."""
+    f32 = np.float32
+    D = V.shape[1]
+    Y, nr = _scored_rows(V, metric)
+    if setup is None:
+        m = min(len(V), 65536)  # setup_direction: the first kDirRows rows
+        S = Y[:m]
     else:
-        Y = V.astype(f32)
-    m = min(len(V), 65536)  # setup_direction: the first kDirRows rows
-    sums = Y[:m].astype(np.float64).sum(0)
+        m = len(setup)
+        assert 0 < m <= 65536, m
+        S, _ = _scored_rows(np.asarray(setup, dtype=f32), metric)
+    sel = slice(None) if maxima is None else maxima
+    sums = S.astype(np.float64).sum(0)
     dirv = (sums / np.sqrt((sums ** 2).sum())).astype(f32)
     mu = (sums / m).astype(f32)
     Z = (Y - mu).astype(f32)
-    zmax = np.abs(Z[:m]).max()
+    zmax = np.abs(Z[:m]).max() if setup is None else np.abs((S - mu).astype(f32)).max()
     sx = f32(1.25 * zmax / 127) if zmax > 0 else f32(1.0)
     t = Z * (f32(1) / sx)
     xh = np.clip(np.rint(t), -127, 127)
     xl = np.clip(np.rint((t - xh) * f32(256)), -127, 127)
     r8 = Z.astype(np.float64) - np.float64(sx) * xh
     r16 = r8 - np.float64(sx) * xl / 256.0
-    R8, R16 = np.sqrt((r8 ** 2).sum(1)).max(), np.sqrt((r16 ** 2).sum(1)).max()
-    M8, M16 = np.abs(r8 @ dirv.astype(np.float64)).max(), np.abs(r16 @ dirv.astype(np.float64)).max()
-    ZA = np.sqrt(((np.float64(sx) * xh) ** 2).sum(1)).max()
-    XL = np.sqrt(((np.float64(sx) * xl / 256.0) ** 2).sum(1)).max()
-    xmax = nr.max()
+    R8, R16 = np.sqrt((r8 ** 2).sum(1))[sel].max(), np.sqrt((r16 ** 2).sum(1))[sel].max()
+    M8, M16 = np.abs(r8 @ dirv.astype(np.float64))[sel].max(), np.abs(r16 @ dirv.astype(np.float64))[sel].max()
+    ZA = np.sqrt(((np.float64(sx) * xh) ** 2).sum(1))[sel].max()
+    XL = np.sqrt(((np.float64(sx) * xl / 256.0) ** 2).sum(1))[sel].max()
+    xmax = nr[sel].max()
     # queries (prep_queries + prep8)
     qn = np.sqrt((Q.astype(np.float64) ** 2).sum(1))
     q = (Q * (1.0 / np.maximum(qn, 1e-8)).astype(f32)[:, None]).astype(f32) if metric == "cosine" else Q.astype(f32)
@@ -73,12 +91,15 @@ def i8_model(V, Q, metric, prec, want_approx=True):
             H = H + np.rint((rinit * (f32(1) / uH)).astype(f32)).astype(np.int64)[:, None]
         if prec == "i8":
             half = (H.astype(f32) * uH).astype(np.float64)
-        else:
-            L = xh.astype(np.int64) @ ql.T.astype(np.int64) + xl.astype(np.int64) @ qh.T.astype(np.int64)
+        else:  # I8X3: L = xh.ql + xl.qh; I8Q (the 16-bit query on the 8-bit rows): xh.ql alone
+            L = xh.astype(np.int64) @ ql.T.astype(np.int64)
+            if prec == "i8x3":
+                L = L + xl.astype(np.int64) @ qh.T.astype(np.int64)
             half = (H.astype(f32) * uH + L.astype(f32) * uL).astype(np.float64)
         approx = half if metric == "cosine" else 2.0 * half
     # eps (vdb_api.cpp fa.*, finish_kernel, prep8 qerr)
     x3 = prec == "i8x3"
+    q16 = x3 or prec == "i8q"  # (prep8_kernel: the query residual is the 16-bit query's)
     R, M = (R16, M16) if x3 else (R8, M8)
     qd = q.astype(np.float64)
     c = qd @ dirv.astype(np.float64)
@@ -88,7 +109,7 @@ def i8_model(V, Q, metric, prec, want_approx=True):
     r8q = np.sqrt(((qd - np.float64(sq) * qh) ** 2).sum(1))
     r16q = np.sqrt(((qd - np.float64(sq) * (qh + ql / 256.0)) ** 2).sum(1))
     qlv = np.sqrt(((np.float64(sq) * ql / 256.0) ** 2).sum(1))
-    e = (ZA + (XL if x3 else 0.0)) * (r16q if x3 else r8q) + (XL * qlv if x3 else 0.0)
+    e = (ZA + (XL if x3 else 0.0)) * (r16q if q16 else r8q) + (XL * qlv if x3 else 0.0)
     e = e + (float(uH) if metric == "euclidean" else 0.0)
     qerr = 1.01 * (e if metric == "cosine" else 2.0 * e)
     eps_rel = 1.01 * 8.0 * 2.0 ** -24
