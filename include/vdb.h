@@ -160,7 +160,9 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "sparse_nnz", "sparse_sets", "sparse_searches", "sparse_queries", "sparse_bad_queries",
  * "hybrid_searches", "hybrid_queries" are described there) and "hybrid_sum_wgs" (workgroups per
  * query of vdb_index_search_hybrid_sum, 0 = auto, 1..512; its stats "hybrid_sum_searches",
- * "hybrid_sum_queries" are described there).  Stats also: "searches", "queries",
+ * "hybrid_sum_queries" are described there).  The numeric columns and predicate masks have no
+ * knob; their stats "column_slots", "column_sets", "filter_calls", "filter_preds" are described at
+ * vdb_index_filter_mask.  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
  * "capacity", "count", "device_bytes", "precision", "searches_fp32" / "searches_bf16x3" /
  * "searches_bf16" / "searches_i8" / "searches_i8x3" / "searches_i8q" (candidate passes run in
@@ -710,6 +712,62 @@ int32_t vdb_index_search_hybrid_sum(vdb_index* idx, const float* queries,
                                     float* out_scores, int64_t* out_indices, double* out_fused,
                                     double* out_dense, double* out_sparse,
                                     int64_t index_offset, void* stream);
+
+/* --- filter operators: numeric columns and predicate masks on the device -------------
+ * Replaces: nothing the reference has.  Its filter is `meta.get(key) == value` alone
+ * (service/optimized_vector_store.py:159-165); range filters ("timestamp >= t", "price between a
+ * and b") are what Qdrant, Milvus, Pinecone, Weaviate and Chroma offer beside equality.  A range
+ * bound usually differs per request, so a cached bitmap never hits: these two calls build the
+ * row_mask of such a filter on the device, from fp64 columns the index holds, for every search call
+ * that takes a row_mask.
+ *
+ * vdb_index_set_column attaches one fp64 value per stored row to `slot` (16 slots, 0..15): values
+ * [n], n == count (else VDB_ERR_INVALID).  NaN = the row has no value; +-inf and +-0 are ordinary
+ * values, so nothing is validated.  NULL with n == 0 detaches the slot.  It takes the exclusive
+ * lock, waits for queued searches, copies and returns when done, as vdb_index_set_groups does;
+ * device memory is read after the work queued on `stream`.  Every successful add, remove and clear
+ * drops all slots; vdb_index_update keeps them.  The slots are independent of the group and sparse
+ * columns.  Stats: "column_slots" (bitmask of the attached slots), "column_sets" (cumulative);
+ * "device_bytes" includes the columns.
+ *
+ * vdb_index_filter_mask evaluates n_preds predicates in one launch.  Predicate p is the AND of the
+ * clauses [pred_offsets[p], pred_offsets[p + 1]): 0 <= n_preds <= 256, at most 8 clauses per
+ * predicate, offsets ascending from 0.  For a row whose value in the clause's column is v:
+ *     has = !(v != v)
+ *     t   = has && (LO_INCL ? v >= lo : v > lo) && (HI_INCL ? v <= hi : v < hi)
+ *     the clause holds iff  NEGATE ? !t : t
+ * so a row without a value fails every plain clause and passes every negated one (MongoDB's $ne).
+ * Equality is [x, x] with both bounds inclusive, "exists" [-inf, +inf] with both inclusive; a
+ * predicate without clauses passes every row.  All compares are plain IEEE fp64 (-0.0 == +0.0, no
+ * rounding): the answer is a set, the same as a numpy restatement bit for bit.
+ *
+ *   clauses, pred_offsets  HOST memory always, whatever `mem` says (a few KB): fully validated
+ *                before anything is launched and copied into the call's workspace staging before
+ *                the call returns
+ *   mem          the memory kind of base_masks, out_masks and out_counts
+ *   base_masks   NULL or [n_preds][W] uint32, W = ceil(count / 32), the row_mask layout
+ *   out_masks    [n_preds][W]: bit r of predicate p is set iff r < count, the predicate holds and
+ *                the bit of base_masks[p] is set; bits at or past count in the last word are
+ *                written as 0; nothing at or past n_preds * W words is written.  Only 4-byte
+ *                alignment is required.  May not alias base_masks.
+ *   out_counts   NULL or [n_preds] int64: the exact number of bits set
+ *
+ * Device-memory calls are stream-ordered and read nothing back, so an output mask can be the
+ * row_mask of a device search queued behind it on the same stream.  Host-memory calls take a
+ * per-search workspace, its stream and pinned staging, as vdb_index_search_range does, and return
+ * with the results in host memory.  Takes the shared lock.  An empty index gives W = 0, counts 0
+ * and VDB_OK.  Errors, all VDB_ERR_INVALID, no stat moves on any: a slot outside 0..15 or one not
+ * attached, unknown flag bits, a NaN bound, more than 8 clauses in a predicate, n_preds outside
+ * 0..256, offsets that decrease or do not start at 0, a NULL out_masks with n_preds > 0 and
+ * count > 0, a bad mem.  Stats: "filter_calls", "filter_preds" (cumulative over successful calls);
+ * "searches", "queries" and every "searches_*" stat stay still. */
+enum { VDB_FILTER_LO_INCL = 1, VDB_FILTER_HI_INCL = 2, VDB_FILTER_NEGATE = 4 };
+typedef struct { int32_t column; int32_t flags; double lo; double hi; } vdb_filter_clause;
+int32_t vdb_index_set_column(vdb_index* idx, int32_t slot, const double* values, int64_t n,
+                             int32_t mem, void* stream);
+int32_t vdb_index_filter_mask(vdb_index* idx, const vdb_filter_clause* clauses, const int32_t* pred_offsets,
+                              int32_t n_preds, const uint32_t* base_masks, int32_t mem,
+                              uint32_t* out_masks, int64_t* out_counts, void* stream);
 
 /* --- MaxSim search: groups ranked by the summed best match per query vector ---------
  * Replaces: nothing the reference has.  Multi-vector ("late interaction") retrieval -- ColBERT /

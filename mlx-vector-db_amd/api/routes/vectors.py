@@ -43,6 +43,7 @@ from fastapi import APIRouter, Depends, HTTPException, Security
 from fastapi.security import HTTPAuthorizationCredentials, HTTPBearer
 from pydantic import BaseModel, Field, model_validator
 
+from service.filter_ops import FilterError
 from service.optimized_vector_store import GROUP_MAX_K, GROUP_MAX_SIZE, MLXVectorStore, MLXVectorStoreConfig
 
 logger = logging.getLogger(__name__)
@@ -465,6 +466,8 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
             return VectorQueryResponse(results=format_query_results(store.config.metric, indices, scores, metas),
                                        query_time_ms=(time.time() - t0) * 1000,
                                        total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except FilterError as e:  # a malformed filter condition is the caller's error (nothing the reference has)
+            raise HTTPException(status_code=400, detail=f"Query failed: {e}")
         except Exception as e:  # the reference turns every error, its own 400s included, into a 500
             logger.error("Error querying vectors: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Query failed: {e}")
@@ -754,6 +757,8 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
             return BatchQueryResponse(results=format_batch_results(store.config.metric, batch),
                                       total_queries=len(request.queries),
                                       avg_query_time_ms=total / len(request.queries))
+        except FilterError as e:  # as /query: a malformed filter condition is a 400
+            raise HTTPException(status_code=400, detail=f"Batch query failed: {e}")
         except Exception as e:  # the reference turns every error, its own 400s included, into a 500
             logger.error("Error in batch query: %s", e)
             raise HTTPException(status_code=500, detail=f"Batch query failed: {e}")
@@ -768,7 +773,9 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
                                              lambda: store.delete_vectors(request.filter_metadata))
             return VectorDeleteResponse(success=True, deleted=res["deleted"], total_vectors=res["total_vectors"],
                                         processing_time_ms=(time.time() - t0) * 1000)
-        except Exception as e:  # as the sibling routes: every error becomes a 500
+        except FilterError as e:  # as /query: a malformed filter condition is a 400
+            raise HTTPException(status_code=400, detail=f"Failed to delete vectors: {e}")
+        except Exception as e:  # as the sibling routes: every other error becomes a 500
             logger.error("Error deleting vectors: %s", e)
             raise HTTPException(status_code=500, detail=f"Failed to delete vectors: {e}")
 

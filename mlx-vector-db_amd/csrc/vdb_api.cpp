@@ -27,6 +27,7 @@
 #include "vdb_subset_plan.h"
 #include "vdb_range_plan.h"
 #include "vdb_group_plan.h"
+#include "vdb_filter_plan.h"
 #include "vdb_mmr_plan.h"
 #include "vdb_fuse_plan.h"
 #include "vdb_maxsim_plan.h"
@@ -116,6 +117,15 @@ struct Workspace {
     // concurrent host searches (the reference's 4-thread executor, api/routes/vectors.py:43)
     // overlap on the device instead of queueing on one index stream
     hipStream_t own = nullptr;
+    // vdb_index_filter_mask: pinned slots for the staged clauses and offsets of a call (one
+    // allocation of kFiltRing x kFilterStageBytes, on first use) and the event after each slot's
+    // upload: a device-memory call returns with its upload only queued, so the next call takes the
+    // next slot, and a slot is rewritten only once its last upload has run
+    static constexpr int kFiltRing = 8;
+    char* filt_io = nullptr;
+    hipEvent_t filt_up[kFiltRing] = {};
+    bool filt_used[kFiltRing] = {};
+    int filt_head = 0;
 };
 
 }  // namespace
@@ -287,6 +297,14 @@ struct vdb_index {
     std::atomic<int64_t> n_hybrid_searches{0}, n_hybrid_queries{0};
     // vdb_index_search_hybrid_sum: calls and queries (successful calls)
     std::atomic<int64_t> n_hybsum_searches{0}, n_hybsum_queries{0};
+    // vdb_index_set_column: the numeric columns, slot s = fp64 [count] (a device copy owned by the
+    // index, NaN = the row has no value), col_mask bit s = slot s is attached; add, remove and clear
+    // drop them all (col_mask = 0), update keeps them; independent of the groups and the sparse column
+    double* cols[kFilterSlots] = {};
+    int64_t col_cap[kFilterSlots] = {};
+    uint32_t col_mask = 0;
+    // vdb_index_set_column / vdb_index_filter_mask: successful calls, and the predicates of those
+    std::atomic<int64_t> n_column_sets{0}, n_filter_calls{0}, n_filter_preds{0};
     int64_t hybsum_wgs = 0;  // knob: workgroups per query of a weighted-sum hybrid search (0 = auto)
     std::atomic<int64_t> n_by_prec[N_PREC] = {{0}, {0}, {0}, {0}, {0}, {0}};  // candidate passes per PREC_* (VDB_PREC_AUTO's choices)
     std::atomic<int64_t> scan_ns{0}, pipe_ns{0}, n_timed{0};
@@ -311,6 +329,9 @@ void free_workspace_memory(Workspace* w) {
     if (w->exact) (void)hipFree(w->exact);
     if (w->host_flag) (void)hipHostFree(w->host_flag);
     if (w->host_io) (void)hipHostFree(w->host_io);
+    if (w->filt_io) (void)hipHostFree(w->filt_io);
+    w->filt_io = nullptr;
+    for (int r = 0; r < Workspace::kFiltRing; ++r) w->filt_used[r] = false;
     w->dev = nullptr;
     w->exact = nullptr;
     w->host_flag = nullptr;
@@ -936,6 +957,8 @@ int32_t vdb_index_destroy(vdb_index* ix) {
         for (int r = 0; r < Workspace::kTRing; ++r)
             for (int e = 0; e < 4; ++e)
                 if (w->tring[r][e]) (void)hipEventDestroy(w->tring[r][e]);
+        for (int r = 0; r < Workspace::kFiltRing; ++r)
+            if (w->filt_up[r]) (void)hipEventDestroy(w->filt_up[r]);
         delete w;
     }
     if (ix->X) (void)hipFree(ix->X);
@@ -957,6 +980,8 @@ int32_t vdb_index_destroy(vdb_index* ix) {
     if (ix->d_group_fb) (void)hipFree(ix->d_group_fb);
     if (ix->sparse_indptr) (void)hipFree(ix->sparse_indptr);
     if (ix->sparse_pairs) (void)hipFree(ix->sparse_pairs);
+    for (int s = 0; s < kFilterSlots; ++s)
+        if (ix->cols[s]) (void)hipFree(ix->cols[s]);
     if (ix->h_totals) (void)hipHostFree(ix->h_totals);
     for (auto& kv : ix->uses) (void)hipEventDestroy(kv.second);
     if (ix->stream) (void)hipStreamDestroy(ix->stream);
@@ -1197,7 +1222,9 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "i8_wide") *value = ix->i8_wide ? 1 : 0;
     else if (n == "device_bytes") {  // the row buffers actually allocated
         const int64_t xb = (int64_t)(ix->cap_rows / 32) * ix->G * BLOCK_FLOATS * 4;  // fp32 X: 4 B per element
-        *value = xb + (xs_ptr(ix) ? xb : 0) + (ix->Xq ? xb / 2 : 0) + (ix->Xh ? xb / 4 : 0) + ix->cap_rows * 20;
+        int64_t cb = 0;  // the numeric columns (vdb_index_set_column), attached or kept for the next attach
+        for (int s = 0; s < kFilterSlots; ++s) cb += ix->cols[s] ? ix->col_cap[s] * 8 : 0;
+        *value = xb + (xs_ptr(ix) ? xb : 0) + (ix->Xq ? xb / 2 : 0) + (ix->Xh ? xb / 4 : 0) + ix->cap_rows * 20 + cb;
     } else if (n == "split_copy") *value = xs_ptr(ix) ? 1 : 0;
     else if (n == "split_copy_builds") *value = ix->n_xs_builds.load();
     else if (n == "rows_removed") *value = ix->n_rows_removed.load();
@@ -1207,6 +1234,10 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "subset_rows") *value = ix->n_subset_rows.load();
     else if (n == "range_searches") *value = ix->n_range_searches.load();
     else if (n == "range_queries") *value = ix->n_range_queries.load();
+    else if (n == "column_slots") *value = ix->col_mask;
+    else if (n == "column_sets") *value = ix->n_column_sets.load();
+    else if (n == "filter_calls") *value = ix->n_filter_calls.load();
+    else if (n == "filter_preds") *value = ix->n_filter_preds.load();
     else if (n == "group_rows") *value = ix->group_set ? ix->group_n : 0;
     else if (n == "group_sets") *value = ix->n_group_sets.load();
     else if (n == "group_searches") *value = ix->n_group_searches.load();
@@ -1449,6 +1480,7 @@ int32_t vdb_index_add(vdb_index* ix, const float* vectors, int64_t n, int32_t me
     ix->count += n;
     ix->group_set = false;  // the group column covered the old rows only
     ix->sparse_set = false;  // and so did the sparse column
+    ix->col_mask = 0;        // and the numeric columns
     ix->auto_hold = 0;  // new rows: VDB_PREC_AUTO tries the one-plane passes again
     ix->auto_fails = 0;
     ix->auto_hold8 = 0;
@@ -1489,6 +1521,7 @@ static int32_t clear_locked(vdb_index* ix) {
     ix->count = 0;
     ix->group_set = false;
     ix->sparse_set = false;
+    ix->col_mask = 0;
     ix->auto_hold = 0;
     ix->auto_fails = 0;
     ix->auto_hold8 = 0;
@@ -1633,6 +1666,7 @@ int32_t vdb_index_remove(vdb_index* ix, const uint32_t* remove_mask, int32_t mem
     ix->count = kept;
     ix->group_set = false;  // the rows moved: the group column no longer lines up
     ix->sparse_set = false;  // nor does the sparse column
+    ix->col_mask = 0;        // nor do the numeric columns
     ix->gen++;
     ix->n_rows_removed += N - kept;
     ix->auto_hold = 0;  // the rows changed: VDB_PREC_AUTO tries the one-plane passes again
@@ -2678,6 +2712,168 @@ int32_t vdb_index_set_groups(vdb_index* ix, const int32_t* groups, int64_t n, in
     ix->group_n = n;
     ix->group_set = true;
     ix->n_group_sets++;
+    return VDB_OK;
+}
+
+static_assert(sizeof(vdb_filter_clause) == sizeof(FilterClause) && sizeof(FilterClause) == 24 &&
+                  offsetof(vdb_filter_clause, column) == offsetof(FilterClause, column) &&
+                  offsetof(vdb_filter_clause, flags) == offsetof(FilterClause, flags) &&
+                  offsetof(vdb_filter_clause, lo) == offsetof(FilterClause, lo) &&
+                  offsetof(vdb_filter_clause, hi) == offsetof(FilterClause, hi),
+              "vdb_filter_clause and FilterClause share one layout");
+static_assert(VDB_FILTER_LO_INCL == kFilterLoIncl && VDB_FILTER_HI_INCL == kFilterHiIncl &&
+                  VDB_FILTER_NEGATE == kFilterNegate,
+              "the flag values of vdb.h and vdb_filter_plan.h agree");
+
+int32_t vdb_index_set_column(vdb_index* ix, int32_t slot, const double* values, int64_t n, int32_t mem, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    if (slot < 0 || slot >= kFilterSlots)
+        return set_error(VDB_ERR_INVALID, "slot must be in [0, %d), got %d", kFilterSlots, slot);
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::shared_mutex> g(ix->mu);
+    if (!filter_column_ok(slot, values != nullptr, n, ix->count))
+        return set_error(VDB_ERR_INVALID, values ? "the column has %lld rows, the index %lld"
+                                                 : "a NULL column detaches: n must be 0 (got %lld)",
+                         (long long)n, (long long)ix->count);
+    // queued device-memory calls on caller streams read the column this call replaces
+    {
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+    }
+    const uint32_t bit = 1u << slot;
+    if (!values) {  // detach
+        ix->col_mask &= ~bit;
+        return VDB_OK;
+    }
+    hipStream_t st = ix->stream;
+    if (n > ix->col_cap[slot] || !ix->cols[slot]) {
+        const int64_t cap = round_up(std::max<int64_t>(n, 1), kRowAlign);
+        double* cnew = nullptr;
+        HIP_TRY(hipMalloc(&cnew, (size_t)cap * sizeof(double)));
+        if (ix->cols[slot]) (void)hipFree(ix->cols[slot]);
+        ix->cols[slot] = cnew;
+        ix->col_cap[slot] = cap;
+    }
+    ix->col_mask &= ~bit;  // until the new column is whole
+    if (n > 0) {
+        if (mem == VDB_MEM_DEVICE) {
+            // the values may still be being written on the caller's stream: the copy starts after that work
+            HIP_TRY(order_after_caller(st, stream));
+        }
+        HIP_TRY(hipMemcpyAsync(ix->cols[slot], values, (size_t)n * sizeof(double),
+                               mem == VDB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    ix->col_mask |= bit;
+    ix->n_column_sets++;
+    return VDB_OK;
+}
+
+int32_t vdb_index_filter_mask(vdb_index* ix, const vdb_filter_clause* clauses, const int32_t* pred_offsets,
+                              int32_t n_preds, const uint32_t* base_masks, int32_t mem, uint32_t* out_masks,
+                              int64_t* out_counts, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    // the clauses and offsets are host memory whatever `mem` says: everything checked before any launch
+    const FilterClause* cl = reinterpret_cast<const FilterClause*>(clauses);
+    int64_t at = 0;
+    uint32_t used = 0;
+    switch (filter_validate(cl, pred_offsets, n_preds, ix->col_mask, &at, &used)) {
+        case kFilterBadPreds:
+            return set_error(VDB_ERR_INVALID, "n_preds must be in [0, %d], got %d", kFilterMaxPreds, n_preds);
+        case kFilterNullArgs: return set_error(VDB_ERR_INVALID, "NULL clauses / pred_offsets pointer");
+        case kFilterBadOffsets:
+            return set_error(VDB_ERR_INVALID, "pred_offsets must start at 0 and ascend (predicate %lld)", (long long)at);
+        case kFilterTooMany:
+            return set_error(VDB_ERR_INVALID, "predicate %lld has more than %d clauses", (long long)at, kFilterMaxClauses);
+        case kFilterBadSlot:
+            return set_error(VDB_ERR_INVALID, "clause %lld: column %d is outside [0, %d)", (long long)at, cl[at].column,
+                             kFilterSlots);
+        case kFilterNotAttached:
+            return set_error(VDB_ERR_INVALID,
+                             "clause %lld: no column is attached to slot %d (vdb_index_set_column; add, remove and "
+                             "clear drop the columns)",
+                             (long long)at, cl[at].column);
+        case kFilterBadFlags:
+            return set_error(VDB_ERR_INVALID, "clause %lld: unknown flag bits 0x%x", (long long)at, (unsigned)cl[at].flags);
+        case kFilterNanBound: return set_error(VDB_ERR_INVALID, "clause %lld: a bound is NaN", (long long)at);
+        default: break;
+    }
+    const int64_t N = ix->count;
+    if (n_preds > 0 && N > 0 && !out_masks) return set_error(VDB_ERR_INVALID, "out_masks is NULL");
+    if (out_masks && base_masks && N > 0 && (const uint32_t*)out_masks == base_masks)
+        return set_error(VDB_ERR_INVALID, "out_masks may not alias base_masks");
+    if (n_preds == 0) {
+        ix->n_filter_calls++;
+        return VDB_OK;
+    }
+    const bool host = mem == VDB_MEM_HOST;
+    const int32_t n_clauses = pred_offsets[n_preds];
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+    const bool based = base_masks != nullptr && N > 0;
+    const FilterScratch sc = filter_scratch(n_preds, N, host, based);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    const size_t mask_bytes = (size_t)n_preds * (size_t)sc.n_words * 4;
+    FilterArgs a{};
+    a.base = based ? base_masks : nullptr;
+    a.out = out_masks;
+    a.counts = reinterpret_cast<unsigned long long*>(out_counts);
+    if (host) {  // the base masks go up in one copy through the pinned staging, the results come down in one
+        if (based) {
+            rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st,
+                          [&](char* h) { std::memcpy(h + (sc.base - sc.in0), base_masks, mask_bytes); });
+            if (rc) return rc;
+            a.base = reinterpret_cast<const uint32_t*>(dev + sc.base);
+        } else {
+            rc = ws_host_io(w, (size_t)(sc.in_bytes + sc.out_bytes));
+            if (rc) return rc;
+        }
+        a.out = reinterpret_cast<uint32_t*>(dev + sc.out_m);
+        a.counts = out_counts ? reinterpret_cast<unsigned long long*>(dev + sc.out_c) : nullptr;
+    }
+    if (a.counts) HIP_TRY(hipMemsetAsync(a.counts, 0, (size_t)n_preds * 8, st));  // (an empty index: all there is)
+    if (N > 0) {
+        // the clauses and offsets: into a pinned slot of the workspace's ring now, up on the stream
+        if (!w->filt_io)
+            HIP_TRY(hipHostMalloc(&w->filt_io, (size_t)Workspace::kFiltRing * kFilterStageBytes, hipHostMallocDefault));
+        const int slot = w->filt_head;
+        w->filt_head = (slot + 1) % Workspace::kFiltRing;
+        if (!w->filt_up[slot]) HIP_TRY(hipEventCreateWithFlags(&w->filt_up[slot], hipEventDisableTiming));
+        if (w->filt_used[slot]) HIP_TRY(hipEventSynchronize(w->filt_up[slot]));
+        char* h = w->filt_io + (size_t)slot * kFilterStageBytes;
+        const FilterStage fs = filter_stage(n_clauses, n_preds);
+        if (n_clauses > 0) std::memcpy(h + fs.clauses, cl, (size_t)n_clauses * sizeof(FilterClause));
+        std::memcpy(h + fs.offsets, pred_offsets, (size_t)(n_preds + 1) * 4);
+        HIP_TRY(hipMemcpyAsync(dev + sc.stage, h, (size_t)fs.bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(w->filt_up[slot], st));
+        w->filt_used[slot] = true;
+        for (int s = 0; s < kFilterSlots; ++s) a.cols[s] = ((used >> s) & 1u) ? ix->cols[s] : nullptr;
+        a.used = used;
+        a.N = N;
+        a.n_words = sc.n_words;
+        a.n_preds = n_preds;
+        a.n_clauses = n_clauses;
+        a.clauses = reinterpret_cast<const FilterClause*>(dev + sc.stage + fs.clauses);
+        a.offsets = reinterpret_cast<const int32_t*>(dev + sc.stage + fs.offsets);
+        HIP_TRY(launch_filter_mask(a, ix->n_cu, st));
+    }
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        if (out_masks && mask_bytes) std::memcpy(out_masks, r + (sc.out_m - sc.out0), mask_bytes);
+        if (out_counts) std::memcpy(out_counts, r + (sc.out_c - sc.out0), (size_t)n_preds * 8);
+    }
+    ix->n_filter_calls++;
+    ix->n_filter_preds += n_preds;
     return VDB_OK;
 }
 

@@ -346,6 +346,22 @@ struct RangeArgs {
 };
 hipError_t launch_range_block(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st);
 
+// Predicate masks (vdb_filter.hip, vdb_index_filter_mask): n_preds predicates (at most 256), predicate
+// p the AND of clauses [offsets[p], offsets[p + 1]) (at most 8 each, n_clauses in all; device copies
+// in the layout of vdb_filter_plan.h FilterClause), over rows [0, N) of the fp64 columns cols[s] of
+// the slots in `used` (NaN = no value).  out [n_preds][n_words] (n_words = ceil(N / 32), the row_mask
+// layout; only 4-byte aligned): bit r of predicate p = r < N, the predicate holds and base (optional,
+// same shape) has the bit; bits at or past N are 0 and nothing at or past n_preds * n_words words is
+// written.  counts (optional, [n_preds], zeroed by the caller on the same stream) += the bits set.
+// One launch; n_cu sizes the grid.
+struct FilterClause;
+struct FilterArgs {
+    const double* cols[16]; uint32_t used; int64_t N; int64_t n_words; int n_preds; int n_clauses;
+    const FilterClause* clauses; const int32_t* offsets;
+    const uint32_t* base; uint32_t* out; unsigned long long* counts;
+};
+hipError_t launch_filter_mask(const FilterArgs& a, int n_cu, hipStream_t st);
+
 // Grouped search (vdb_group.hip, vdb_index_search_groups).  The column's bitmap: bit r of word r / 32
 // = row r < n has a group id >= 0 (n_words words written whole), *n_valid += those rows; and out =
 // a & b over n_words words (the caller's row mask with that bitmap), *n_set += the bits set in it.

@@ -37,6 +37,15 @@ GRAPH_EF_MAX = 256
 FUSION_IDS = {"rrf": 0, "max": 1}
 # largest k vdb_index_search_hybrid_sum accepts (csrc/vdb_hybsum_plan.h kHybsumMaxK)
 HYBRID_SUM_MAX_K = 1024
+# vdb_index_set_column / vdb_index_filter_mask (include/vdb.h VDB_FILTER_*, csrc/vdb_filter_plan.h)
+FILTER_LO_INCL = 1
+FILTER_HI_INCL = 2
+FILTER_NEGATE = 4
+FILTER_SLOTS = 16
+FILTER_MAX_PREDS = 256
+FILTER_MAX_CLAUSES = 8
+# the layout of vdb_filter_clause: int32 column, int32 flags, fp64 lo, fp64 hi (24 bytes)
+FILTER_CLAUSE_DTYPE = np.dtype([("column", "<i4"), ("flags", "<i4"), ("lo", "<f8"), ("hi", "<f8")])
 
 # Every symbol include/vdb.h declares (tests/test_abi.py checks the .so exports them).
 EXPORTED_SYMBOLS = (
@@ -46,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_add", "vdb_index_count", "vdb_index_clear", "vdb_index_remove", "vdb_index_update",
     "vdb_index_get_vectors",
     "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
+    "vdb_index_set_column", "vdb_index_filter_mask",
     "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim",
     "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_index_search_hybrid_sum", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
@@ -111,6 +121,8 @@ def load_library():
                                               c_vp, c_i64, c_vp]),
             "vdb_index_search_range": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64,
                                                c_vp]),
+            "vdb_index_set_column": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i32, c_vp]),
+            "vdb_index_filter_mask": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
             "vdb_index_set_groups": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
             "vdb_index_search_groups": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
                                                 c_vp]),
@@ -184,6 +196,21 @@ def device_count() -> int:
 
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
+
+
+def pack_predicates(predicates):
+    """A list of lists of ``(slot, lo, hi, flags)`` -> (clauses FILTER_CLAUSE_DTYPE [n], offsets
+    int32 [P + 1]): the arguments of vdb_index_filter_mask.  Nothing is validated here but the
+    shape of a clause; the library checks the rest."""
+    flat, offs = [], [0]
+    for pred in predicates:
+        for cl in pred:
+            if len(cl) != 4:
+                raise ValueError(f"a clause is (slot, lo, hi, flags), got {cl!r}")
+            slot, lo, hi, flags = cl
+            flat.append((int(slot), int(flags), float(lo), float(hi)))
+        offs.append(len(flat))
+    return np.array(flat, dtype=FILTER_CLAUSE_DTYPE).reshape(-1), np.asarray(offs, dtype=np.int32)
 
 
 def rows_to_bitmap(mask_or_rows, count: int) -> np.ndarray:
@@ -541,6 +568,61 @@ class NativeIndex:
             ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, int(cap), ctypes.c_void_p(out_counts_ptr),
             ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_scores_ptr or None),
             ctypes.c_void_p(out_keys_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
+
+    # -- numeric columns and predicate masks ---------------------------------------
+    def set_column(self, slot: int, values) -> None:
+        """include/vdb.h vdb_index_set_column, host memory: attach one fp64 value per row to
+        ``slot`` (0..15; ``len(values) == count``; NaN = the row has no value).  ``None`` detaches
+        the slot.  Every add, remove and clear drops all slots; an update keeps them."""
+        if values is None:
+            _check(self._lib.vdb_index_set_column(self._h, int(slot), None, 0, MEM_HOST, None))
+            return
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float64).reshape(-1))
+        # (an empty array still attaches -- to an empty index: a pointer the library never reads)
+        _check(self._lib.vdb_index_set_column(self._h, int(slot), _ptr(v) if v.size else _ptr(np.zeros(1, np.float64)),
+                                              v.size, MEM_HOST, None))
+
+    def set_column_device(self, slot: int, ptr: int, n: int, stream: int = 0) -> None:
+        """vdb_index_set_column with a device-memory fp64 column, read after the work queued on
+        ``stream``."""
+        _check(self._lib.vdb_index_set_column(self._h, int(slot), ctypes.c_void_p(ptr or None), int(n), MEM_DEVICE,
+                                              ctypes.c_void_p(stream or None)))
+
+    def filter_mask(self, predicates, base_masks: Optional[np.ndarray] = None):
+        """include/vdb.h vdb_index_filter_mask, host memory: ``predicates`` is a list of lists of
+        ``(slot, lo, hi, flags)`` clauses, each inner list ANDed (an empty one passes every row).
+        ``base_masks``: None or uint32 [P, W] ANDed into the result.  Returns (masks uint32 [P, W]
+        in the row_mask layout, W = ceil(count / 32); counts int64 [P], the bits set)."""
+        clauses, offsets = pack_predicates(predicates)
+        P = offsets.size - 1
+        W = (self.count() + 31) // 32
+        base_p = None
+        if base_masks is not None:
+            base = np.ascontiguousarray(base_masks, dtype=np.uint32)
+            if base.size != P * W:
+                raise ValueError(f"base_masks needs {P} x {W} uint32 words, got {base.size}")
+            base_p = _ptr(base) if base.size else None
+        masks = np.zeros((P, W), dtype=np.uint32)
+        counts = np.zeros(P, dtype=np.int64)
+        _check(self._lib.vdb_index_filter_mask(
+            self._h, _ptr(clauses) if clauses.size else None, _ptr(offsets), P, base_p, MEM_HOST,
+            _ptr(masks) if masks.size else None, _ptr(counts) if P else None, None))
+        return masks, counts
+
+    def filter_mask_device(self, clauses: np.ndarray, pred_offsets: np.ndarray, base_ptr: int, out_masks_ptr: int,
+                           out_counts_ptr: int = 0, stream: int = 0) -> None:
+        """vdb_index_filter_mask with device-memory masks and counts (uint32 [P, W] and int64 [P]);
+        ``clauses`` (FILTER_CLAUSE_DTYPE) and ``pred_offsets`` (int32 [P + 1]) are host arrays, as
+        the call always takes them.  Stream-ordered, nothing is read back: an output mask can be
+        the ``mask_ptr`` of a ``search_device`` queued behind it on the same stream."""
+        cl = np.ascontiguousarray(clauses, dtype=FILTER_CLAUSE_DTYPE).reshape(-1)
+        offs = np.ascontiguousarray(pred_offsets, dtype=np.int32).reshape(-1)
+        if offs.size < 1:
+            raise ValueError("pred_offsets needs n_preds + 1 entries")
+        _check(self._lib.vdb_index_filter_mask(
+            self._h, _ptr(cl) if cl.size else None, _ptr(offs), offs.size - 1, ctypes.c_void_p(base_ptr or None),
+            MEM_DEVICE, ctypes.c_void_p(out_masks_ptr or None), ctypes.c_void_p(out_counts_ptr or None),
+            ctypes.c_void_p(stream or None)))
 
     # -- grouped search ----------------------------------------------------------
     def set_groups(self, groups) -> None:

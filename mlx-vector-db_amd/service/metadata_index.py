@@ -15,6 +15,12 @@ Semantics are exactly ``meta.get(key) == value``:
   * ``value is None`` also matches rows that lack the key (``get`` returns None);
   * a filter value that is unhashable or NaN (where dict lookup and ``==``
     disagree) falls back to the reference's scan for that pair.
+
+A value that is a condition (service/filter_ops.py: a non-empty dict whose keys all start with
+``$``) is answered from the same postings: $eq / $ne / $in / $nin / $exists as unions and
+complements of posting lists, the range operators over the key's distinct numeric values
+(``range_rows``); ``numeric_column`` is the fp64 column of a key that the device evaluates range
+clauses on (include/vdb.h vdb_index_set_column).
 """
 from __future__ import annotations
 
@@ -25,6 +31,8 @@ from collections import OrderedDict
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
+
+from .filter_ops import RANGE_OPS, canonical_key, has_range_ops, is_condition, parse_condition
 
 
 def _hashable(v: Any) -> bool:
@@ -45,6 +53,7 @@ class MetadataIndex:
         self._seen_rows: Dict[str, int] = {}  # key -> rows holding it (for the None / missing case)
         self._n = 0
         self._rows: List[Dict] = []
+        self.version = 0  # bumped by every extend, remove, replace and clear: what a derived column is tagged with
         self._lock = threading.Lock()
         self._cache: "OrderedDict[Tuple, Tuple[np.ndarray, int]]" = OrderedDict()
 
@@ -58,6 +67,7 @@ class MetadataIndex:
             self._n = 0
             self._rows = []
             self._cache.clear()
+            self.version += 1
 
     def extend(self, metadata: List[Dict]) -> None:
         """Index rows [n, n + len(metadata)) (called under the store's write lock)."""
@@ -79,6 +89,7 @@ class MetadataIndex:
             self._rows.extend(metadata)
             self._n = r
             self._cache.clear()
+            self.version += 1
 
     def remove(self, rows) -> int:
         """Drop the given rows (ids in [0, len), any order, repeats allowed): the survivors keep
@@ -92,6 +103,7 @@ class MetadataIndex:
             if ids.size and (ids[0] < 0 or ids[-1] >= n):
                 raise ValueError(f"row ids must be in [0, {n}), got [{int(ids[0])}, {int(ids[-1])}]")
             self._cache.clear()
+            self.version += 1
             if ids.size == 0:
                 return 0
             gone = np.zeros(n, bool)
@@ -165,6 +177,7 @@ class MetadataIndex:
             if ids and (min(ids) < 0 or max(ids) >= self._n):
                 raise ValueError(f"row ids must be in [0, {self._n}), got [{min(ids)}, {max(ids)}]")
             self._cache.clear()
+            self.version += 1
             if len(self._rows) < self._n:  # (fewer metadata entries than rows: the rest hold nothing)
                 self._rows.extend({} for _ in range(self._n - len(self._rows)))
             lose: Dict[Tuple[Any, Any], set] = {}
@@ -226,11 +239,114 @@ class MetadataIndex:
             rows = np.union1d(rows, missing)
         return rows[rows < n]
 
+    # ---- filter operators (service/filter_ops.py) ---------------------------------------------
+    def _has_key(self, key: Any, n: int) -> np.ndarray:
+        """bool [n]: the row's metadata holds ``key`` (the lock held).  The postings give the rows
+        that hold it with a hashable value; a value the postings skip (unhashable, NaN) is found
+        only by a pass over the first n metadata dicts, as the ``value is None`` branch of
+        ``_pair_rows`` makes: ``$exists`` costs O(n) on the host, once per cached filter."""
+        has = np.zeros(n, bool)
+        for vals in (self._post.get(key, {}) if _hashable(key) else {}).values():
+            a = np.frombuffer(vals, dtype=np.int64)
+            has[a[a < n]] = True
+        for i in range(min(n, len(self._rows))):  # rows holding the key with a value the postings skip
+            m = self._rows[i]
+            if isinstance(m, dict) and key in m and not _hashable(m[key]):
+                has[i] = True
+        return has
+
+    def _numeric_postings(self, key: Any, n: int):
+        """(value, rows < n) for every distinct int or float value of ``key`` that is not a bool
+        (NaN is held by no posting), from the key's postings (the lock held).  True, 1 and 1.0 --
+        and False, 0 and 0.0 -- share one posting, as they are equal and hash alike: the rows of
+        those two postings are told apart by the type of the value they hold."""
+        by_val = self._post.get(key) if _hashable(key) else None
+        for val, lst in (by_val or {}).items():
+            if not isinstance(val, (int, float)):
+                continue
+            a = np.frombuffer(lst, dtype=np.int64)
+            a = a[a < n]
+            if val == 0 or val == 1:
+                keep = [int(r) for r in a.tolist() if not isinstance(self._rows[r].get(key), bool)]
+                if not keep:
+                    continue
+                a = np.asarray(keep, dtype=np.int64)
+                val = self._rows[keep[0]].get(key)
+            if a.size:
+                yield val, a
+
+    def numeric_column(self, key: Any, n: int) -> Tuple[np.ndarray, bool]:
+        """(float64 [n], exact): row r's value for ``key`` when it is an int or float that is not a
+        bool and not NaN, NaN otherwise ("the row has no value": the column the device's predicate
+        masks take, include/vdb.h vdb_index_set_column).  ``exact`` is False when some value v has
+        float(v) != v (an int beyond 2^53): the device would then compare a rounded value.  Built
+        from the postings of ``key`` alone, O(rows holding it), not by a scan of the dicts."""
+        col = np.full(max(int(n), 0), np.nan, dtype=np.float64)
+        exact = True
+        with self._lock:
+            for val, a in self._numeric_postings(key, n):
+                try:
+                    f = float(val)
+                except OverflowError:
+                    f, exact = (math.inf if val > 0 else -math.inf), False
+                if f != val:
+                    exact = False
+                col[a] = f
+        return col, exact
+
+    def _range_rows(self, key: Any, ops, n: int) -> np.ndarray:
+        """Sorted rows < n whose value for ``key`` is a number that every range operator of ``ops``
+        holds for, by Python's comparisons over the key's distinct posting values (the lock held)."""
+        hits = [a for val, a in self._numeric_postings(key, n) if all(RANGE_OPS[op](val, x) for op, x in ops)]
+        return np.sort(np.concatenate(hits)) if hits else np.zeros(0, np.int64)
+
+    def range_rows(self, key: Any, ops, n: int) -> np.ndarray:
+        """The host evaluation of a range condition: ``ops`` = [(op, bound)] with op among $gt,
+        $gte, $lt, $lte, ANDed; O(distinct values + matching rows)."""
+        with self._lock:
+            return self._range_rows(key, ops, n)
+
+    def _cond_rows(self, key: Any, ops, n: int) -> np.ndarray:
+        """Sorted rows < n for which every operator of a condition on ``key`` holds (the lock held)."""
+
+        def complement(r):
+            keep = np.ones(n, bool)
+            keep[r] = False
+            return np.nonzero(keep)[0]
+
+        def union(values):
+            r = np.zeros(0, np.int64)
+            for x in values:
+                r = np.union1d(r, self._pair_rows(key, x, n))
+            return r
+
+        rows = None
+        ranges = [(op, x) for op, x in ops if op in RANGE_OPS]
+        for op, x in ops:
+            if op in RANGE_OPS:
+                continue
+            if op == "$eq":
+                r = self._pair_rows(key, x, n)
+            elif op == "$ne":
+                r = complement(self._pair_rows(key, x, n))
+            elif op == "$in":
+                r = union(x)
+            elif op == "$nin":
+                r = complement(union(x))
+            else:  # $exists
+                has = self._has_key(key, n)
+                r = np.nonzero(has if x else ~has)[0]
+            rows = r if rows is None else np.intersect1d(rows, r, assume_unique=True)
+        if ranges:
+            r = self._range_rows(key, ranges, n)
+            rows = r if rows is None else np.intersect1d(rows, r, assume_unique=True)
+        return rows if rows is not None else np.arange(n, dtype=np.int64)
+
     def _match_rows(self, filt: Dict, n: int) -> np.ndarray:
-        """Sorted rows < n matching every pair of ``filt`` (the lock held)."""
+        """Sorted rows < n matching every pair and condition of ``filt`` (the lock held)."""
         rows = None
         for k, v in filt.items():
-            pr = self._pair_rows(k, v, n)
+            pr = self._cond_rows(k, parse_condition(k, v), n) if is_condition(v) else self._pair_rows(k, v, n)
             rows = pr if rows is None else np.intersect1d(rows, pr, assume_unique=True)
             if rows.size == 0:
                 break
@@ -247,11 +363,12 @@ class MetadataIndex:
 
     def bitmap(self, filt: Dict, n: int) -> Tuple[np.ndarray, int]:
         """(uint32 words of the rows < n matching every pair, match count)."""
-        try:
-            ck: Optional[Tuple] = (tuple(sorted(filt.items(), key=lambda kv: repr(kv[0]))), n)
-            hash(ck)
+        try:  # (condition dicts become tuples; a filter without conditions keys as it always did)
+            ck: Optional[Tuple] = (canonical_key(filt), n)
         except TypeError:
             ck = None
+        if has_range_ops(filt):
+            ck = None  # a range bound usually differs per request: it would only evict the bitmaps that recur
         with self._lock:
             if ck is not None and ck in self._cache:
                 self._cache.move_to_end(ck)

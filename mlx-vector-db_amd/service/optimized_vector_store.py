@@ -26,6 +26,7 @@ import json
 import logging
 import os
 import collections
+from collections import OrderedDict
 import shutil
 import threading
 import time
@@ -35,7 +36,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
-from . import _vdb
+from . import _vdb, filter_ops
 from .metadata_index import MetadataIndex
 from .persistence import StoreFiles
 
@@ -184,14 +185,28 @@ class MLXVectorStoreConfig:
 
 
 def _filter_key(filt: Dict):
-    """Grouping key of a filter: equal for filters holding the same pairs (as the bitmap cache
-    keys them); a filter with an unhashable value is its own group."""
+    """Grouping key of a filter: equal for filters holding the same pairs and conditions (as the
+    bitmap cache keys them; a condition dict is canonicalised into a tuple, so equal conditions
+    written as separate dict objects share a group); a filter with an unhashable value is its own
+    group."""
     try:
-        key = tuple(sorted(filt.items(), key=lambda kv: repr(kv[0])))
-        hash(key)
-        return key
+        return filter_ops.canonical_key(filt)
     except TypeError:
         return ("unhashable", id(filt))
+
+
+def _mask_rows(mask: np.ndarray, n: int) -> np.ndarray:
+    """The rows < n a uint32 bitmap marks, ascending (int64): the row list of a mask the device
+    built.  Only the non-zero words are unpacked: a pass over n / 32 words, then work per set word,
+    not per row (a row list is taken for filters that match a few rows of many)."""
+    words = np.ascontiguousarray(mask, np.uint32).reshape(-1)[:(n + 31) // 32]
+    nz = np.nonzero(words)[0]
+    if nz.size == 0:
+        return np.zeros(0, np.int64)
+    bits = np.unpackbits(words[nz].astype("<u4").view(np.uint8).reshape(-1, 4), axis=1, bitorder="little")
+    w, b = np.nonzero(bits)
+    rows = nz[w].astype(np.int64) * 32 + b
+    return rows[rows < n]
 
 
 def _as_matrix(vectors: Any) -> np.ndarray:
@@ -383,6 +398,12 @@ class MLXVectorStore:
         self._sparse_tag: Optional[Tuple] = None
         self._sparse_terms = 0
         self._sparse_sets = -1
+        # range filters: metadata key -> (slot, (rows, update count, metadata version), exact) for the numeric columns
+        # attached to the index's 16 slots, least recently used first, and the index's
+        # "column_sets" after the last attach made here
+        self._column_lock = threading.Lock()
+        self._col_slots: "OrderedDict[Any, Tuple[Optional[int], Tuple, bool]]" = OrderedDict()
+        self._column_sets = -1
         self._hnsw_index = None
         self._files = StoreFiles(self.store_path)
         self._coalescer = _QueryCoalescer(lambda Q, k, filters=None: self._search_filtered(
@@ -487,7 +508,7 @@ class MLXVectorStore:
             n = self._vector_count
             if n == 0:
                 return {"deleted": 0, "total_vectors": 0}
-            mask, hits = self._meta_index.bitmap(filter_metadata, n)
+            mask, hits = self._filter_masks([filter_metadata], n)[0]
             if hits == 0:
                 return {"deleted": 0, "total_vectors": n}
             return self._delete_locked(mask)
@@ -664,6 +685,8 @@ class MLXVectorStore:
             if use_hnsw and self.config.enable_hnsw and h is not None and h.is_loaded:
                 # service/optimized_vector_store.py:120-143: hnswlib distances, k*10 candidates
                 # when filtering, brute force on any failure
+                # (the filter is parsed once, outside the try: a malformed condition is the caller's error)
+                matches = filter_ops.compile_filter(filter_metadata) if filter_metadata else None
                 try:
                     candidate_k = k * 10 if filter_metadata else k
                     indices, distances = h.search(q[None, :], k=candidate_k)
@@ -675,7 +698,7 @@ class MLXVectorStore:
                     for i, idx in enumerate(indices):
                         if idx < len(self._metadata):
                             meta = self._metadata[int(idx)]
-                            if all(meta.get(key) == value for key, value in filter_metadata.items()):
+                            if matches(meta):
                                 hits.append((int(idx), float(distances[i]), meta))
                         if len(hits) == k:
                             break
@@ -693,11 +716,14 @@ class MLXVectorStore:
                     return self._coalescer.query(q, k)
                 # a filter the planner searches as a row list joins a batch of such filters (one
                 # device call for all of them); any other keeps its own masked search
-                eligible = self._meta_index.bitmap(filter_metadata, self._vector_count)[1]
-                if eligible == 0:
-                    return [], [], []
-                if self._subset_ok(eligible):
-                    return self._coalescer.query(q, k, filter_metadata)
+                # (a filter with range operators is evaluated once, by the planner below: its mask
+                # is cached nowhere, so a look at its count here would be a second device call)
+                if not filter_ops.has_range_ops(filter_metadata):
+                    eligible = self._filter_masks([filter_metadata], self._vector_count)[0][1]
+                    if eligible == 0:
+                        return [], [], []
+                    if self._subset_ok(eligible):
+                        return self._coalescer.query(q, k, filter_metadata)
             return self._brute_force_search(q[None, :], k, filter_metadata)[0]
 
     def batch_query(self, query_vectors: Union[np.ndarray, Any], k: int = 10,
@@ -744,6 +770,143 @@ class MLXVectorStore:
         return (frac > 0.0 and len(self._devices()) == 1 and hasattr(self._index, "search_rows")
                 and eligible <= frac * self._vector_count)
 
+    # ---- filter operators ------------------------------------------------------------
+    def _filter_masks(self, filters: List[Dict], n: int) -> List[Tuple[np.ndarray, int]]:
+        """(uint32 words over rows [0, n), eligible count) for each filter (read or write lock
+        held): the one place a filter becomes a row_mask.  A filter without conditions
+        (service/filter_ops.py) is exactly ``MetadataIndex.bitmap``, cache included.  A filter
+        with range operators is split: its pairs and posting operators ($eq, $ne, $in, $nin,
+        $exists) are a host bitmap, the predicate's base mask, and the range operators of each key
+        fold into one clause on that key's numeric column; all such filters of the call go into
+        ONE ``filter_mask`` call (include/vdb.h vdb_index_filter_mask), a predicate each, in
+        chunks of 256.  The host evaluates the range operators instead on a multi-device store,
+        when a column or a bound is not exact in fp64 or a filter needs more than 8 clauses: the
+        answer is the same either way."""
+        out: List[Optional[Tuple[np.ndarray, int]]] = [None] * len(filters)
+        dev = []  # (position, the filter, its base filter, {key: folded interval})
+        for i, f in enumerate(filters):
+            plain, conds = filter_ops.split_filter(f)  # (a malformed condition raises here)
+            ranges = {k: filter_ops.fold_range(filter_ops.range_ops(ops)) for k, ops in conds.items()
+                      if filter_ops.range_ops(ops)}
+            if not ranges or not self._device_filter_ok(ranges, n):
+                out[i] = self._meta_index.bitmap(f, n)
+                continue
+            base = dict(plain)
+            for k, ops in conds.items():
+                post = filter_ops.posting_ops(ops)
+                if post:
+                    base[k] = dict(post)
+            dev.append((i, f, base, ranges))
+        chunk, keys = [], set()
+        for item in dev:
+            more = keys | set(item[3])
+            if chunk and (len(chunk) == _vdb.FILTER_MAX_PREDS or len(more) > _vdb.FILTER_SLOTS):
+                self._device_filter_chunk(chunk, n, out)
+                chunk, more = [], set(item[3])
+            chunk.append(item)
+            keys = more
+        if chunk:
+            self._device_filter_chunk(chunk, n, out)
+        return out
+
+    def _filter_rows(self, filt: Dict, mask: np.ndarray, n: int) -> np.ndarray:
+        """The ascending row list of a filter whose mask ``_filter_masks`` gave: from the postings
+        in O(matching rows) as ever for a filter without range operators, off the mask's non-zero
+        words for one with them (its rows exist nowhere else; evaluating it again would cost more)."""
+        if filter_ops.has_range_ops(filt):
+            return _mask_rows(mask, n)
+        return self._meta_index.rows(filt, n)
+
+    def _device_filter_ok(self, ranges: Dict, n: int) -> bool:
+        """The device takes these range clauses: a single-device store with rows, at most 8 keys
+        and every bound unchanged by the conversion to fp64 (the columns are checked at attach)."""
+        return (n > 0 and len(self._devices()) == 1 and hasattr(self._index, "filter_mask")
+                and len(ranges) <= _vdb.FILTER_MAX_CLAUSES
+                and all(filter_ops.float_exact(lo) and filter_ops.float_exact(hi) for lo, _, hi, _ in ranges.values()))
+
+    def _attach_columns(self, keys, n: int) -> Dict[Any, Optional[int]]:
+        """Make every key's numeric column one of the index's 16 (``_column_lock`` held) -> key ->
+        slot, None for a key whose column is not exact in fp64.  An entry is kept while the row
+        count and the rows' contents stay as they were and the index still holds what was attached
+        here (an add, a delete and a clear drop the slots; an upsert may change a value; the
+        metadata index's version moves with each of them, so a key found inexact is looked at again
+        once the rows have changed).  The table holds at most 16 keys, inexact ones included: the
+        least recently used gives way to a 17th."""
+        tag = (n, self._index.stat("rows_updated"), self._meta_index.version)
+        sets = self._index.stat("column_sets")
+        if sets != self._column_sets:
+            self._col_slots.clear()  # somebody else attached a column: nothing here is known to hold
+            self._column_sets = sets
+        held = self._index.stat("column_slots")
+        for key in [k for k, (slot, t, _) in self._col_slots.items()
+                    if t != tag or (slot is not None and not (held >> slot) & 1)]:
+            del self._col_slots[key]
+        slots: Dict[Any, Optional[int]] = {}
+        for key in keys:
+            if key in self._col_slots:
+                self._col_slots.move_to_end(key)
+                slots[key] = self._col_slots[key][0]
+                continue
+            col, exact = self._meta_index.numeric_column(key, n)
+            slot = None
+            while len(self._col_slots) >= _vdb.FILTER_SLOTS:
+                victim = next(k for k in self._col_slots if k not in keys)
+                del self._col_slots[victim]
+            if exact:
+                used = {s for s, _, _ in self._col_slots.values()}
+                slot = next(s for s in range(_vdb.FILTER_SLOTS) if s not in used)
+                self._index.set_column(slot, col)
+                self._column_sets = self._index.stat("column_sets")
+            self._col_slots[key] = (slot, tag, exact)
+            slots[key] = slot
+        return slots
+
+    def _device_filter_chunk(self, chunk, n: int, out: List) -> None:
+        """One ``filter_mask`` call for up to 256 filters with range clauses (at most 16 keys
+        between them); a filter on a column that is not exact goes to the host instead."""
+        W = (n + 31) // 32
+        keys = sorted({k for _, _, _, ranges in chunk for k in ranges}, key=repr)
+        with self._column_lock:  # attach and evaluate as one step: no other reader evicts a slot in between
+            slots = self._attach_columns(keys, n)
+            preds, bases, where = [], [], []
+            for i, f, base, ranges in chunk:
+                if any(slots[k] is None for k in ranges):
+                    out[i] = self._meta_index.bitmap(f, n)
+                    continue
+                if base:
+                    words, eligible = self._meta_index.bitmap(base, n)
+                    if eligible == 0:
+                        out[i] = (np.zeros(W, np.uint32), 0)
+                        continue
+                else:
+                    words = None
+                preds.append([(slots[k], float(lo), float(hi),
+                               (_vdb.FILTER_LO_INCL if li else 0) | (_vdb.FILTER_HI_INCL if hi_i else 0))
+                              for k, (lo, li, hi, hi_i) in ranges.items()])
+                bases.append(words)
+                where.append(i)
+            if not preds:
+                return
+            base_masks = None
+            if any(b is not None for b in bases):
+                base_masks = np.empty((len(preds), W), np.uint32)
+                for p, b in enumerate(bases):
+                    base_masks[p] = 0xFFFFFFFF if b is None else b[:W]
+            masks, counts = self._index.filter_mask(preds, base_masks)
+        for p, i in enumerate(where):
+            out[i] = (masks[p], int(counts[p]))
+
+    def count_matching(self, filter_metadata: Optional[Dict]) -> int:
+        """How many stored rows match ``filter_metadata`` (the filter semantics of ``query``,
+        conditions included); without a filter, the number of rows."""
+        with _Read(self._rw):
+            n = self._vector_count
+            if n == 0 or not filter_metadata:
+                if filter_metadata:
+                    filter_ops.split_filter(filter_metadata)  # (still checked)
+                return n
+            return int(self._filter_masks([filter_metadata], n)[0][1])
+
     def _search_filtered(self, Q: np.ndarray, k: int, filters: List[Optional[Dict]]):
         """The planner of every brute-force read (called with the read lock held): ``filters``
         holds one entry per query, a dict or None.  Queries are grouped by filter.  A group without
@@ -767,17 +930,19 @@ class MLXVectorStore:
         for b, f in enumerate(filters):
             groups.setdefault(_filter_key(f) if f else None, (f if f else None, []))[1].append(b)
         masked, subset = [], []
+        # posting lists maintained at add time, not the reference's O(N) scan (:159-165); the range
+        # clauses of all the groups that carry any in one device call (_filter_masks)
+        filtered = [(filt, members) for filt, members in groups.values() if filt is not None]
+        bitmaps = self._filter_masks([filt for filt, _ in filtered], n)
         for filt, members in groups.values():
             if filt is None:
                 masked.append((None, n, members))
-                continue
-            # posting lists maintained at add time, not the reference's O(N) scan (:159-165)
-            mask, eligible = self._meta_index.bitmap(filt, n)
+        for (filt, members), (mask, eligible) in zip(filtered, bitmaps):
             if eligible == 0:
                 for b in members:
                     out[b] = ([], [], [])
             elif self._subset_ok(eligible):
-                subset.append((filt, eligible, members))
+                subset.append((filt, mask, eligible, members))
             else:
                 masked.append((mask, eligible, members))
 
@@ -799,12 +964,12 @@ class MLXVectorStore:
             scores, idx = self._index.search(take(members), kk, row_mask=mask)
             fill(members, scores, idx)
         if subset:
-            kk = min(k, max(e for _, e, _ in subset))  # (a shorter list pads its rows with -1)
+            kk = min(k, max(e for _, _, e, _ in subset))  # (a shorter list pads its rows with -1)
             if kk > 1024:
                 raise ValueError(f"k={k} exceeds the device top-k limit of 1024")
-            members = [b for _, _, mem in subset for b in mem]
-            lists = [self._meta_index.rows(filt, n) for filt, _, _ in subset]
-            qlist = np.concatenate([np.full(len(mem), li, np.int32) for li, (_, _, mem) in enumerate(subset)])
+            members = [b for _, _, _, mem in subset for b in mem]
+            lists = [self._filter_rows(filt, mask, n) for filt, mask, _, _ in subset]
+            qlist = np.concatenate([np.full(len(mem), li, np.int32) for li, (_, _, _, mem) in enumerate(subset)])
             scores, idx = self._index.search_rows(take(members), kk, lists, query_list=qlist)
             fill(members, scores, idx)
         return out
@@ -876,7 +1041,7 @@ class MLXVectorStore:
             raise ValueError(f"Dimension mismatch: query has {Q.shape[1]} dims, store holds {self._dim}")
         if not filter_metadata:
             return None
-        mask, eligible = self._meta_index.bitmap(filter_metadata, self._vector_count)
+        mask, eligible = self._filter_masks([filter_metadata], self._vector_count)[0]
         return mask if eligible else False
 
     def _range_search(self, Q: np.ndarray, thresholds, filter_metadata: Optional[Dict], limit: Optional[int]):
@@ -987,7 +1152,7 @@ class MLXVectorStore:
                 return out
             # group_size > 1: every returned group's own rows, searched as row lists (one list per
             # distinct group of the batch, shared between the queries that returned it)
-            filt_rows = self._meta_index.rows(filter_metadata, n) if filter_metadata else None
+            filt_rows = self._filter_rows(filter_metadata, mask, n) if filter_metadata else None
             list_of: Dict[int, int] = {}
             lists, members, qlist = [], [], []
             for b in range(B):
@@ -1233,7 +1398,7 @@ class MLXVectorStore:
         when nothing matches the filter (no device call is needed)."""
         if not filter_metadata:
             return None
-        mask, eligible = self._meta_index.bitmap(filter_metadata, self._vector_count)
+        mask, eligible = self._filter_masks([filter_metadata], self._vector_count)[0]
         return mask if eligible else False
 
     def hybrid_query(self, query_vector: Union[np.ndarray, Any], sparse, k: int = 10, fetch_k: Optional[int] = None,
@@ -1482,7 +1647,7 @@ class MLXVectorStore:
                 raise RuntimeError(_NO_OPERATOR_MSG)
             mask = None
             if filter_metadata:
-                mask, eligible = self._meta_index.bitmap(filter_metadata, n)
+                mask, eligible = self._filter_masks([filter_metadata], n)[0]
                 if not eligible:
                     return empty
             scores, idx = self._index.search_recommend(pos, neg if any(g.size for g in neg) else None, k, row_mask=mask)
