@@ -160,7 +160,9 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "sparse_nnz", "sparse_sets", "sparse_searches", "sparse_queries", "sparse_bad_queries",
  * "hybrid_searches", "hybrid_queries" are described there) and "hybrid_sum_wgs" (workgroups per
  * query of vdb_index_search_hybrid_sum, 0 = auto, 1..512; its stats "hybrid_sum_searches",
- * "hybrid_sum_queries" are described there).  The numeric columns and predicate masks have no
+ * "hybrid_sum_queries" are described there) and "hamming_wgs" (workgroups per query block of
+ * vdb_index_search_hamming, 0 = auto, 1..512; the code column's and its stats "code_rows",
+ * "code_bytes", "code_sets", "hamming_searches", "hamming_queries" are described there).  The numeric columns and predicate masks have no
  * knob; their stats "column_slots", "column_sets", "filter_calls", "filter_preds" are described at
  * vdb_index_filter_mask.  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
@@ -712,6 +714,50 @@ int32_t vdb_index_search_hybrid_sum(vdb_index* idx, const float* queries,
                                     float* out_scores, int64_t* out_indices, double* out_fused,
                                     double* out_dense, double* out_sparse,
                                     int64_t index_offset, void* stream);
+
+/* --- Binary codes: a bit vector per row, exact Hamming top-k ---------------------------
+ * Replaces: nothing the reference has (its nearest code is the `mx.argsort` top-k of
+ * service/optimized_vector_store.py:176-183, over fp32 scores).  Binary embeddings (Cohere's
+ * `ubinary`, sentence-transformers' binary quantisation), perceptual image hashes and SimHash /
+ * MinHash signatures are rows of bits ranked by Hamming distance: FAISS' IndexBinaryFlat, Milvus'
+ * BIN_FLAT with HAMMING, Qdrant's and Weaviate's binary quantisation with rescoring.
+ *
+ * vdb_index_set_codes attaches one code of n_bytes bytes per stored row: codes [n][n_bytes] row-major,
+ * n == count and 1 <= n_bytes <= 1024 (8 to 8 192 bits), else VDB_ERR_INVALID.  Every byte pattern
+ * is a code, so nothing in the data is validated.  codes == NULL with n == 0 detaches the column.
+ * The call takes the exclusive lock, waits for queued searches, copies the column (the caller's
+ * array may be reused on return; device memory is read after the work queued on `stream`) and
+ * returns when done.  Every successful add, remove and clear drops the column; vdb_index_update
+ * keeps it; it is independent of the group, sparse and numeric columns.  The device copy is tiled:
+ * 64 rows per tile, 64-bit words, word-major inside a tile.  Stats: "code_rows" (rows
+ * attached, 0 = none), "code_bytes" (bytes per row, 0 = none), "code_sets" (cumulative);
+ * "device_bytes" includes the column.
+ *
+ * vdb_index_search_hamming: the k nearest rows of each query code.
+ *   queries      [n_queries, n_bytes] uint8, of the attached width; 0 <= n_queries <= 65 535
+ *   k            1..1024
+ *   out_distances [n_queries, k] int32; out_indices [n_queries, k] int64
+ *   row_mask, mem, index_offset, stream: as vdb_index_search_rows; all pointers of one memory kind.
+ * Contract: d(b, r) = popcount(queries[b] XOR codes[r]) over the 8 * n_bytes bits.  Candidates: the
+ * rows below count whose mask bit is set.  Ranking by (d asc, row asc); the first min(k, candidates)
+ * slots hold out_distances = d and out_indices = row + index_offset, later slots distance -1 and
+ * index -1.  Distances are integers, so the result is exact as it stands and the same bytes for
+ * every metric, precision setting and memory kind: the fp32 rows and the candidate copies are not
+ * read.  Errors, before anything is launched, both memory kinds, all VDB_ERR_INVALID: no column
+ * attached, k or n_queries out of range, a NULL queries / out_distances / out_indices with
+ * n_queries > 0, a bad mem (no stat moves).  n_queries == 0 is VDB_OK.  Any bytes are a query, so
+ * there is no bad query; device-memory calls are stream-ordered and read nothing back.  Host-memory
+ * calls take a per-search workspace, its stream and pinned staging, as vdb_index_search_sparse does.
+ * An empty index with an empty column attached gives "no result" everywhere.  Takes the shared lock.
+ * Knob "hamming_wgs": workgroups per block of queries, 0 = auto, 1..512 (results identical).  Stats:
+ * "hamming_searches", "hamming_queries" (cumulative over successful calls); "searches", "queries"
+ * and every "searches_*" stat stay still. */
+int32_t vdb_index_set_codes(vdb_index* idx, const uint8_t* codes, int64_t n, int32_t n_bytes,
+                            int32_t mem, void* stream);
+int32_t vdb_index_search_hamming(vdb_index* idx, const uint8_t* queries, int32_t n_queries, int32_t k,
+                                 const uint32_t* row_mask, int32_t mem,
+                                 int32_t* out_distances, int64_t* out_indices,
+                                 int64_t index_offset, void* stream);
 
 /* --- filter operators: numeric columns and predicate masks on the device -------------
  * Replaces: nothing the reference has.  Its filter is `meta.get(key) == value` alone

@@ -117,6 +117,23 @@ class VectorSparseQuery(BaseModel):
     sparse_key: str = Field(default="sparse", description="Metadata key holding each row's sparse vector")
 
 
+class VectorBinaryQuery(BaseModel):
+    """The ``k`` rows whose binary code (stored in the row's metadata under ``binary_key``, as hex) is
+    nearest in Hamming distance to ``code`` (single) or to each of ``codes`` (batch).  With
+    ``rescore_vector`` (single only) the nearest min(k * oversample, 1024) rows are re-ranked by their
+    exact dense score.  The store checks the limits (k at most 1024, one code width); a value
+    outside them is a 400."""
+    user_id: str
+    model_id: str
+    code: Optional[str] = Field(default=None, description="The query's code, hex")
+    codes: Optional[List[str]] = Field(default=None, description="A batch of query codes, hex")
+    k: int = Field(default=10, description="Rows returned")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    binary_key: str = Field(default="code", description="Metadata key holding each row's code")
+    rescore_vector: Optional[List[float]] = Field(default=None, description="Dense vector to re-rank the fetched rows by")
+    oversample: int = Field(default=4, description="Rows fetched per row returned when rescoring")
+
+
 class VectorHybridQuery(BaseModel):
     """Dense and sparse retrieval fused by weighted reciprocal rank: the best ``fetch_k`` rows (null:
     min(200, max(k, 4 k))) for ``query`` and the best ``fetch_k`` for ``sparse`` are fused per row,
@@ -270,6 +287,15 @@ class VectorFusedQueryResponse(BaseModel):
 class VectorSparseQueryResponse(BaseModel):
     # best first: {"metadata", "sparse_score" (the dot product), "rank"}
     results: List[Dict[str, Any]]
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorBinaryQueryResponse(BaseModel):
+    # nearest first: {"metadata", "distance" (Hamming, an integer), "rank"}, with rescore_vector also
+    # "similarity_score"; a batch request answers with "batch_results", one such list per code
+    results: List[Dict[str, Any]]
+    batch_results: Optional[List[List[Dict[str, Any]]]] = None
     query_time_ms: float
     total_vectors_searched: int
 
@@ -622,6 +648,53 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in sparse query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Sparse query failed: {e}")
+
+    @router.post("/binary_query", response_model=VectorBinaryQueryResponse)
+    async def binary_query_vectors(request: VectorBinaryQuery, api_key: str = Depends(auth)):
+        """The ``k`` rows nearest in Hamming distance, nearest first; ``code`` for one query, ``codes``
+        for a batch.  A bad request (neither or both given, bad hex, a width other than the stored
+        one, k outside its limits: the store's ValueError) is a 400, an unsupported store a 501,
+        anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if (request.code is None) == (request.codes is None):
+                raise HTTPException(status_code=400, detail="Give either code or codes")
+            if request.codes is not None and request.rescore_vector is not None:
+                raise HTTPException(status_code=400, detail="rescore_vector goes with a single code")
+            loop = asyncio.get_running_loop()
+
+            def shape(t):
+                out = [{"metadata": m, "distance": d, "rank": i + 1} for i, (m, d) in enumerate(zip(t[2], t[1]))]
+                if len(t) > 3:
+                    for r, sc in zip(out, t[3]):
+                        r["similarity_score"] = sc
+                return out
+
+            if request.code is not None:
+                got = await loop.run_in_executor(
+                    mgr._executor, lambda: store.binary_query(request.code, k=request.k, filter_metadata=request.filter_metadata,
+                                                              binary_key=request.binary_key,
+                                                              rescore_vector=request.rescore_vector,
+                                                              oversample=request.oversample))
+                results, batch = shape(got), None
+            else:
+                got = await loop.run_in_executor(
+                    mgr._executor, lambda: store.batch_binary_query(request.codes, k=request.k,
+                                                                    filter_metadata=request.filter_metadata,
+                                                                    binary_key=request.binary_key))
+                results, batch = [], [shape(t) for t in got]
+            return VectorBinaryQueryResponse(results=results, batch_results=batch, query_time_ms=(time.time() - t0) * 1000,
+                                             total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Binary query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Binary query failed: {e}")
+        except Exception as e:
+            logger.error("Error in binary query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Binary query failed: {e}")
 
     @router.post("/hybrid_query", response_model=VectorHybridQueryResponse)
     async def hybrid_query_vectors(request: VectorHybridQuery, api_key: str = Depends(auth)):

@@ -32,6 +32,7 @@
 #include "vdb_fuse_plan.h"
 #include "vdb_maxsim_plan.h"
 #include "vdb_sparse_plan.h"
+#include "vdb_hamming_plan.h"
 #include "vdb_hybsum_plan.h"
 #include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
@@ -294,6 +295,15 @@ struct vdb_index {
     // vdb_index_search_sparse / _hybrid: calls and queries (successful calls); the queries the sparse
     // kernel found bad are counted on the device (d_xmax + kSparseBadWord)
     std::atomic<int64_t> n_sparse_sets{0}, n_sparse_searches{0}, n_sparse_queries{0};
+    // vdb_index_set_codes: the binary code column, code_bytes bytes per stored row, kept in the tiled
+    // layout of vdb_hamming_plan.h (codes: code_cap_words 64-bit words, owned by the index); add,
+    // remove and clear drop it (code_set = false), update keeps it; independent of the other columns
+    uint64_t* codes = nullptr;
+    int64_t code_cap_words = 0, code_n = 0;
+    int32_t code_bytes = 0;
+    bool code_set = false;
+    int64_t hamming_wgs = 0;  // knob: workgroups per query block of a Hamming search (0 = auto)
+    std::atomic<int64_t> n_code_sets{0}, n_hamming_searches{0}, n_hamming_queries{0};
     std::atomic<int64_t> n_hybrid_searches{0}, n_hybrid_queries{0};
     // vdb_index_search_hybrid_sum: calls and queries (successful calls)
     std::atomic<int64_t> n_hybsum_searches{0}, n_hybsum_queries{0};
@@ -980,6 +990,7 @@ int32_t vdb_index_destroy(vdb_index* ix) {
     if (ix->d_group_fb) (void)hipFree(ix->d_group_fb);
     if (ix->sparse_indptr) (void)hipFree(ix->sparse_indptr);
     if (ix->sparse_pairs) (void)hipFree(ix->sparse_pairs);
+    if (ix->codes) (void)hipFree(ix->codes);
     for (int s = 0; s < kFilterSlots; ++s)
         if (ix->cols[s]) (void)hipFree(ix->cols[s]);
     if (ix->h_totals) (void)hipHostFree(ix->h_totals);
@@ -1120,6 +1131,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "sparse_wgs must be in [0, %d] (0 = auto)", kSparseMaxSeg);
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->sparse_wgs = value;
+    } else if (n == "hamming_wgs") {
+        if (value < 0 || value > kHamMaxSeg)
+            return set_error(VDB_ERR_INVALID, "hamming_wgs must be in [0, %d] (0 = auto)", kHamMaxSeg);
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->hamming_wgs = value;
     } else if (n == "hybrid_sum_wgs") {
         if (value < 0 || value > kHybsumMaxSeg)
             return set_error(VDB_ERR_INVALID, "hybrid_sum_wgs must be in [0, %d] (0 = auto)", kHybsumMaxSeg);
@@ -1224,6 +1240,7 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
         const int64_t xb = (int64_t)(ix->cap_rows / 32) * ix->G * BLOCK_FLOATS * 4;  // fp32 X: 4 B per element
         int64_t cb = 0;  // the numeric columns (vdb_index_set_column), attached or kept for the next attach
         for (int s = 0; s < kFilterSlots; ++s) cb += ix->cols[s] ? ix->col_cap[s] * 8 : 0;
+        cb += ix->codes ? ix->code_cap_words * 8 : 0;  // the code column (vdb_index_set_codes), likewise
         *value = xb + (xs_ptr(ix) ? xb : 0) + (ix->Xq ? xb / 2 : 0) + (ix->Xh ? xb / 4 : 0) + ix->cap_rows * 20 + cb;
     } else if (n == "split_copy") *value = xs_ptr(ix) ? 1 : 0;
     else if (n == "split_copy_builds") *value = ix->n_xs_builds.load();
@@ -1280,6 +1297,11 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "sparse_sets") *value = ix->n_sparse_sets.load();
     else if (n == "sparse_searches") *value = ix->n_sparse_searches.load();
     else if (n == "sparse_queries") *value = ix->n_sparse_queries.load();
+    else if (n == "code_rows") *value = ix->code_set ? ix->code_n : 0;
+    else if (n == "code_bytes") *value = ix->code_set ? ix->code_bytes : 0;
+    else if (n == "code_sets") *value = ix->n_code_sets.load();
+    else if (n == "hamming_searches") *value = ix->n_hamming_searches.load();
+    else if (n == "hamming_queries") *value = ix->n_hamming_queries.load();
     else if (n == "hybrid_searches") *value = ix->n_hybrid_searches.load();
     else if (n == "hybrid_queries") *value = ix->n_hybrid_queries.load();
     else if (n == "hybrid_sum_searches") *value = ix->n_hybsum_searches.load();
@@ -1480,6 +1502,7 @@ int32_t vdb_index_add(vdb_index* ix, const float* vectors, int64_t n, int32_t me
     ix->count += n;
     ix->group_set = false;  // the group column covered the old rows only
     ix->sparse_set = false;  // and so did the sparse column
+    ix->code_set = false;    // and the code column
     ix->col_mask = 0;        // and the numeric columns
     ix->auto_hold = 0;  // new rows: VDB_PREC_AUTO tries the one-plane passes again
     ix->auto_fails = 0;
@@ -1521,6 +1544,7 @@ static int32_t clear_locked(vdb_index* ix) {
     ix->count = 0;
     ix->group_set = false;
     ix->sparse_set = false;
+    ix->code_set = false;
     ix->col_mask = 0;
     ix->auto_hold = 0;
     ix->auto_fails = 0;
@@ -1666,6 +1690,7 @@ int32_t vdb_index_remove(vdb_index* ix, const uint32_t* remove_mask, int32_t mem
     ix->count = kept;
     ix->group_set = false;  // the rows moved: the group column no longer lines up
     ix->sparse_set = false;  // nor does the sparse column
+    ix->code_set = false;    // nor does the code column
     ix->col_mask = 0;        // nor do the numeric columns
     ix->gen++;
     ix->n_rows_removed += N - kept;
@@ -3861,6 +3886,147 @@ int32_t vdb_index_search_hybrid_sum(vdb_index* ix, const float* queries, const i
     }
     ix->n_hybsum_searches++;
     ix->n_hybsum_queries += B;
+    return VDB_OK;
+}
+
+int32_t vdb_index_set_codes(vdb_index* ix, const uint8_t* codes, int64_t n, int32_t n_bytes, int32_t mem, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::shared_mutex> g(ix->mu);
+    switch (hamming_column_args(codes != nullptr, n, n_bytes, ix->count)) {
+        case kHamColBadRows:
+            return set_error(VDB_ERR_INVALID, codes ? "the code column has %lld rows, the index %lld"
+                                                    : "a NULL column detaches: n must be 0 (got %lld)",
+                             (long long)n, (long long)ix->count);
+        case kHamColBadWidth:
+            return set_error(VDB_ERR_INVALID, "n_bytes must be in [1, %d], got %d", kHamMaxBytes, n_bytes);
+        default: break;
+    }
+    // queued device-memory searches on caller streams read the column this call replaces
+    {
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+    }
+    if (!codes) {  // detach
+        ix->code_set = false;
+        return VDB_OK;
+    }
+    hipStream_t st = ix->stream;
+    const int64_t words = ham_packed_words(n, ham_words(n_bytes));
+    if (words > ix->code_cap_words || !ix->codes) {
+        uint64_t* cnew = nullptr;
+        const int64_t cap = std::max<int64_t>(words, 64);
+        HIP_TRY(hipMalloc(&cnew, (size_t)cap * sizeof(uint64_t)));
+        if (ix->codes) (void)hipFree(ix->codes);
+        ix->codes = cnew;
+        ix->code_cap_words = cap;
+    }
+    ix->code_set = false;  // until the new column is whole
+    if (n > 0) {
+        const uint8_t* src = codes;
+        uint8_t* up = nullptr;
+        if (mem == VDB_MEM_HOST) {  // the row-major bytes go up as they are; the pack kernel tiles them
+            HIP_TRY(hipMalloc(&up, (size_t)n * n_bytes));
+            const hipError_t e = hipMemcpyAsync(up, codes, (size_t)n * n_bytes, hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) {
+                (void)hipFree(up);
+                HIP_TRY(e);
+            }
+            src = up;
+        } else {
+            // the codes may still be being written on the caller's stream: the pack starts after that work
+            HIP_TRY(order_after_caller(st, stream));
+        }
+        hipError_t e = launch_hamming_pack(src, n, n_bytes, ix->codes, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (up) (void)hipFree(up);
+        HIP_TRY(e);
+    }
+    ix->code_n = n;
+    ix->code_bytes = n_bytes;
+    ix->code_set = true;
+    ix->n_code_sets++;
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_hamming(vdb_index* ix, const uint8_t* queries, int32_t B, int32_t k, const uint32_t* row_mask,
+                                 int32_t mem, int32_t* out_distances, int64_t* out_indices, int64_t index_offset,
+                                 void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // everything checked before any launch (any bytes are a query: the queries themselves need none)
+    const bool column = ix->code_set && ix->code_n == N;
+    switch (hamming_validate_call(B, k, queries != nullptr, out_distances != nullptr, out_indices != nullptr, mem, column)) {
+        case kHamBadCount: return set_error(VDB_ERR_INVALID, "n_queries must be in [0, %d], got %d", kHamMaxQueries, B);
+        case kHamBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", kHamMaxK, k);
+        case kHamBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind");
+        case kHamNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/output pointer");
+        case kHamNoColumn: return set_error(VDB_ERR_INVALID, "no code column is attached (vdb_index_set_codes)");
+        default: break;
+    }
+    if (B == 0) return VDB_OK;
+    const bool host = mem == VDB_MEM_HOST;
+    // as vdb_index_search_sparse: the caller's stream (device memory: NULL = the null stream), or for
+    // a host-memory call without one the stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const int n_bytes = ix->code_bytes;
+    const int qb = ham_block(k, B);
+    const int n_blocks = ham_n_blocks(B, qb);
+    const int n_seg = N > 0 ? ham_n_seg(ix->hamming_wgs, N, n_blocks, ix->n_cu) : 1;
+    const HammingScratch sc = hamming_scratch(B, n_bytes, k, qb, n_seg, N, host, masked);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    HammingArgs a{};
+    a.queries = queries;
+    a.mask = masked ? row_mask : nullptr;
+    a.out_d = out_distances;
+    a.out_i = out_indices;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * n_bytes);
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+        });
+        if (rc) return rc;
+        a.queries = reinterpret_cast<const uint8_t*>(dev + sc.q);
+        a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.out_d = reinterpret_cast<int32_t*>(dev + sc.out_d);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+    }
+    a.codes = ix->codes;
+    a.N = N;
+    a.n_bytes = n_bytes;
+    a.W = ham_words(n_bytes);
+    a.n_queries = B;
+    a.k = k;
+    a.KE = ham_ke(k);
+    a.done = reinterpret_cast<int*>(dev + sc.done);
+    a.lk = n_seg > 1 ? reinterpret_cast<float*>(dev + sc.lk) : nullptr;
+    a.li = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.li) : nullptr;
+    a.mk = n_seg > 1 ? reinterpret_cast<float*>(dev + sc.mk) : nullptr;
+    a.mi = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.mi) : nullptr;
+    a.index_offset = index_offset;
+    // the per-block counters start at zero (the kernel leaves them so; a grown workspace is fresh)
+    if (n_seg > 1) HIP_TRY(hipMemsetAsync(a.done, 0, (size_t)n_blocks * sizeof(int), st));
+    // (an empty index: no row is read, every slot "no result")
+    HIP_TRY(launch_hamming_search(a, qb, n_seg, st));
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_distances, r + (sc.out_d - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+    }
+    ix->n_hamming_searches++;
+    ix->n_hamming_queries += B;
     return VDB_OK;
 }
 

@@ -473,6 +473,26 @@ hipError_t launch_sparse_search(const SparseArgs& a, int n_queries, int n_seg, h
 hipError_t launch_hybrid_sets(int64_t* offs, double* weights, int n_queries, double w_dense, double w_sparse,
                               hipStream_t st);
 
+// The binary code column and the Hamming search (vdb_hamming.hip, vdb_index_set_codes /
+// vdb_index_search_hamming).  Pack: codes [n][n_bytes] row-major bytes in device memory -> packed
+// [ceil(n / 64)][W][64] 64-bit words (vdb_hamming_plan.h), pad bytes and pad rows zero.
+hipError_t launch_hamming_pack(const uint8_t* codes, int64_t n, int n_bytes, uint64_t* packed, hipStream_t st);
+// Search: queries [n_queries][n_bytes] bytes in device memory (any bytes are a query).  Row r < N
+// is a candidate when mask (optional, the row_mask layout) has its bit; the best k by (distance asc,
+// row asc) go to out_d / out_i [b * k + e], distance -1 / index -1 behind them.  Grid (n_seg, query
+// blocks of qb = ham_block(k, n_queries)); with n_seg > 1 the workgroup that finishes a block last
+// merges the segments' lists lk / li [n_queries][n_seg][KE] through mk / mi [n_queries][KE] (done
+// [blocks]: zero on entry, zero again on exit).  N == 0 is allowed (no row is read).
+struct HammingArgs {
+    const uint64_t* codes; int64_t N; int n_bytes; int W;
+    const uint8_t* queries; int n_queries;
+    const uint32_t* mask; int k; int KE;
+    float* lk; uint32_t* li; float* mk; uint32_t* mi; int* done;
+    int32_t* out_d; int64_t* out_i; int64_t index_offset;
+};
+size_t hamming_search_lds_bytes(int qb, int W, int KE, int n_seg);
+hipError_t launch_hamming_search(const HammingArgs& a, int qb, int n_seg, hipStream_t st);
+
 // Weighted-sum hybrid search (vdb_hybsum.hip, vdb_index_search_hybrid_sum).  Query b is the dense
 // vector Q[b] (qn64[b]: its canonical norm) and the sparse entries [q_indptr[b], q_indptr[b + 1]) of
 // q_terms / q_weights, in device memory, read under the clamp and the checks of vdb_sparse_plan.h

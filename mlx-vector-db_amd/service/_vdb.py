@@ -57,7 +57,8 @@ EXPORTED_SYMBOLS = (
     "vdb_index_search", "vdb_index_search_rows", "vdb_index_search_range",
     "vdb_index_set_column", "vdb_index_filter_mask",
     "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim",
-    "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_index_search_hybrid_sum", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_index_search_hybrid_sum",
+    "vdb_index_set_codes", "vdb_index_search_hamming", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -143,6 +144,8 @@ def load_library():
             "vdb_index_search_hybrid_sum": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, ctypes.c_double,
                                                     ctypes.c_double, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
                                                     c_vp]),
+            "vdb_index_set_codes": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
+            "vdb_index_search_hamming": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -852,6 +855,60 @@ class NativeIndex:
             ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, ctypes.c_void_p(out_scores_ptr or None),
             ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_fused_ptr or None),
             ctypes.c_void_p(out_hits_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
+
+    # -- binary codes and Hamming search ---------------------------------------------
+    @staticmethod
+    def _codes(codes, what: str) -> np.ndarray:
+        c = np.asarray(codes)
+        if c.dtype != np.uint8:
+            raise ValueError(f"{what} must be uint8, got dtype {c.dtype}")
+        if c.ndim != 2:
+            raise ValueError(f"{what} must be 2-d [rows, n_bytes], got shape {c.shape}")
+        return np.ascontiguousarray(c)
+
+    def set_codes(self, codes) -> None:
+        """include/vdb.h vdb_index_set_codes, host memory: attach one binary code per row, ``codes``
+        uint8 ``[count, n_bytes]`` with 1 <= n_bytes <= 1024 (byte j holds bits 8j..8j+7, the order of
+        ``np.packbits``).  ``codes=None`` detaches the column.  Every add, remove and clear drops it;
+        an update keeps it.  A column the library refuses raises ValueError."""
+        if codes is None:
+            _check(self._lib.vdb_index_set_codes(self._h, None, 0, 0, MEM_HOST, None))
+            return
+        c = self._codes(codes, "codes")
+        # (an empty column still needs a pointer: NULL means detach)
+        p = _ptr(c) if c.size else _ptr(np.zeros(1, dtype=np.uint8))
+        _check(self._lib.vdb_index_set_codes(self._h, p, c.shape[0], c.shape[1], MEM_HOST, None))
+
+    def set_codes_device(self, codes_ptr: int, n: int, n_bytes: int, stream: int = 0) -> None:
+        """vdb_index_set_codes with a device-memory column (uint8 [n, n_bytes]), read after the work
+        queued on ``stream``."""
+        _check(self._lib.vdb_index_set_codes(self._h, ctypes.c_void_p(codes_ptr or None), int(n), int(n_bytes), MEM_DEVICE,
+                                             ctypes.c_void_p(stream or None)))
+
+    def search_hamming(self, queries, k: int, mask: Optional[np.ndarray] = None, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_hamming, host memory: ``queries`` uint8 ``[B, n_bytes]`` of
+        the attached width; the rows whose ``mask`` bit is set rank by (Hamming distance asc, row asc).
+        Returns (distances i32 [B,k], indices i64 [B,k]); slots past min(k, candidates) are -1 / -1.
+        Needs a column (``set_codes``); ``k`` outside [1, 1024] raises ValueError."""
+        q = self._codes(queries, "queries")
+        width = self.stat("code_bytes")
+        if q.shape[0] and width and q.shape[1] != width:
+            raise ValueError(f"queries are {q.shape[1]} bytes wide, the attached codes {width}")
+        B, k = q.shape[0], int(k)
+        dist = np.empty((B, max(k, 0)), dtype=np.int32)  # (a bad k is the library's to refuse)
+        idx = np.empty((B, max(k, 0)), dtype=np.int64)
+        m, mask_p = self._mask_ptr(mask)
+        _check(self._lib.vdb_index_search_hamming(self._h, _ptr(q) if q.size else None, B, k, mask_p, MEM_HOST,
+                                                  _ptr(dist), _ptr(idx), int(index_offset), None))
+        return dist, idx
+
+    def search_hamming_device(self, queries_ptr: int, n_queries: int, k: int, out_dist_ptr: int, out_idx_ptr: int,
+                              mask_ptr: int = 0, index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_hamming with device-memory arguments; stream-ordered, nothing is read back."""
+        _check(self._lib.vdb_index_search_hamming(
+            self._h, ctypes.c_void_p(queries_ptr or None), int(n_queries), int(k), ctypes.c_void_p(mask_ptr or None),
+            MEM_DEVICE, ctypes.c_void_p(out_dist_ptr or None), ctypes.c_void_p(out_idx_ptr or None), int(index_offset),
+            ctypes.c_void_p(stream or None)))
 
     # -- sparse and hybrid search ----------------------------------------------------
     @staticmethod

@@ -107,6 +107,53 @@ def _sparse_pair(value, what: str):
     return idx, val.astype(np.float32)
 
 
+# binary_query: the most rows per query and the widest code (include/vdb.h vdb_index_search_hamming)
+BINARY_MAX_K = 1024
+BINARY_MAX_BYTES = 1024
+
+
+def normalize_code(value, what: str) -> np.ndarray:
+    """A binary code -> uint8 [n_bytes]: a hex string of 2 * n_bytes characters, ``bytes``, or a
+    sequence of ints 0..255.  Byte j holds bits 8j..8j+7 (``np.packbits`` order)."""
+    if isinstance(value, str):
+        try:
+            code = np.frombuffer(bytes.fromhex(value), dtype=np.uint8)
+        except ValueError:
+            raise ValueError(f"{what} is not a hex string of whole bytes") from None
+    elif isinstance(value, (bytes, bytearray, memoryview)):
+        code = np.frombuffer(bytes(value), dtype=np.uint8)
+    else:
+        a = np.asarray(value)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu") or (a.size and (int(a.min()) < 0 or int(a.max()) > 255)):
+            raise ValueError(f"{what} must be a hex string, bytes or a list of ints 0..255")
+        code = a.astype(np.uint8)
+    if not 1 <= code.size <= BINARY_MAX_BYTES:
+        raise ValueError(f"{what} must hold 1..{BINARY_MAX_BYTES} bytes, got {code.size}")
+    return code
+
+
+def build_code_column(metadata: List[Dict], n: int, binary_key: str = "code"):
+    """The column ``vdb_index_set_codes`` takes, from the first ``n`` rows' metadata -> (codes uint8
+    [n, n_bytes], have uint32 row_mask of the rows that carry a code, n_bytes); n_bytes 0: no row has
+    one.  All codes must have one width (ValueError); a row without the key gets a zero code."""
+    found = {}
+    for r in range(n):
+        m = metadata[r] if r < len(metadata) else None
+        v = m.get(binary_key) if isinstance(m, dict) else None
+        if v is not None:
+            found[r] = normalize_code(v, f"row {r}: metadata[{binary_key!r}]")
+    widths = {c.size for c in found.values()}
+    if len(widths) > 1:
+        raise ValueError(f"the codes under metadata[{binary_key!r}] have different widths: {sorted(widths)} bytes")
+    n_bytes = widths.pop() if widths else 0
+    codes = np.zeros((n, n_bytes), dtype=np.uint8)
+    have = np.zeros((n + 31) // 32, dtype=np.uint32)
+    for r, c in found.items():
+        codes[r] = c
+        have[r >> 5] |= np.uint32(1 << (r & 31))
+    return codes, have, n_bytes
+
+
 def build_sparse_column(metadata: List[Dict], n: int, sparse_key: str = "sparse"):
     """The CSR column ``vdb_index_set_sparse`` takes, from the first ``n`` rows' metadata: row r's
     sparse vector is ``metadata[r][sparse_key]`` (``{"indices": [...], "values": [...]}``, sorted
@@ -398,6 +445,13 @@ class MLXVectorStore:
         self._sparse_tag: Optional[Tuple] = None
         self._sparse_terms = 0
         self._sparse_sets = -1
+        # binary_query: the one code column attached to the index, (key, rows, update count), the
+        # mask of the rows that have a code, its width and the index's "code_sets" when it was attached
+        self._code_lock = threading.Lock()
+        self._code_tag: Optional[Tuple] = None
+        self._code_mask: Optional[np.ndarray] = None
+        self._code_bytes = 0
+        self._code_sets = -1
         # range filters: metadata key -> (slot, (rows, update count, metadata version), exact) for the numeric columns
         # attached to the index's 16 slots, least recently used first, and the index's
         # "column_sets" after the last attach made here
@@ -1327,6 +1381,93 @@ class MLXVectorStore:
                 out.append((ib, scores[b][valid].astype(np.float64).tolist(),
                             [meta[i] if i < len(meta) else {} for i in ib], fused[b][valid].tolist(),
                             hits[b][valid].tolist()))
+            return out
+
+    # ---- binary query -------------------------------------------------------------------
+    def _attach_codes(self, binary_key: str) -> int:
+        """Make the rows' codes under the metadata key ``binary_key`` the code column attached to the
+        index (read lock and _code_lock held) -> the width in bytes (0: no row has a code, nothing is
+        searched).  Kept under ``_attach_sparse``'s tag rule."""
+        n = self._vector_count
+        tag = (binary_key, n, self._index.stat("rows_updated"))
+        if self._code_tag == tag and self._index.stat("code_rows") == n \
+                and self._index.stat("code_sets") == self._code_sets:
+            return self._code_bytes
+        codes, have, n_bytes = build_code_column(self._metadata, n, binary_key)
+        self._code_tag = None
+        if n_bytes == 0:  # no row has a code: no other key's column stays attached
+            if self._index.stat("code_rows"):
+                self._index.set_codes(None)
+        else:
+            self._index.set_codes(codes)
+            self._code_tag, self._code_bytes, self._code_mask = tag, n_bytes, have
+            self._code_sets = self._index.stat("code_sets")
+        return n_bytes
+
+    def binary_query(self, code, k: int = 10, filter_metadata: Optional[Dict] = None, binary_key: str = "code",
+                     rescore_vector=None, oversample: int = 4) -> Tuple:
+        """The ``k`` rows whose binary code (metadata key ``binary_key``: a hex string, ``bytes`` or a
+        list of ints 0..255; byte j holds bits 8j..8j+7) is nearest to ``code`` in Hamming distance ->
+        (indices, distances, metadata), nearest first, ties to the lower row id; a row without a code is
+        never returned.  Exact, on the device (include/vdb.h vdb_index_search_hamming).  With
+        ``rescore_vector`` the nearest min(k * oversample, 1024) rows are fetched and the call returns
+        the exact dense top-k of that set for the vector -> (indices, distances, metadata, scores),
+        best dense score first.  The reference has no such read."""
+        rv = None if rescore_vector is None else [rescore_vector]
+        return self.batch_binary_query([code], k, filter_metadata, binary_key, rv, oversample)[0]
+
+    def batch_binary_query(self, codes, k: int = 10, filter_metadata: Optional[Dict] = None, binary_key: str = "code",
+                           rescore_vectors=None, oversample: int = 4) -> List[Tuple]:
+        """``binary_query`` for a list of codes from one device call: one tuple per query."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("binary query is not supported on a multi-device store")
+        k, oversample = int(k), int(oversample)
+        if not 1 <= k <= BINARY_MAX_K:
+            raise ValueError(f"k must be in [1, {BINARY_MAX_K}], got {k}")
+        if oversample < 1:
+            raise ValueError(f"oversample must be >= 1, got {oversample}")
+        qs = [normalize_code(c, "the query's code") for c in codes]
+        B = len(qs)
+        R = None
+        if rescore_vectors is not None:
+            R = np.stack([np.asarray(_as_matrix(v), dtype=np.float32).reshape(-1) for v in rescore_vectors]) if B else None
+            if B and R.shape[0] != B:
+                raise ValueError(f"{B} codes need {B} rescore vectors, got {R.shape[0]}")
+        empty = [([], [], [], []) if rescore_vectors is not None else ([], [], []) for _ in range(B)]
+        with _Read(self._rw):
+            if self._vector_count == 0 or B == 0:
+                return empty
+            mask = self._sparse_mask(filter_metadata)
+            if mask is False:
+                return empty
+            fetch = k if R is None else min(k * oversample, BINARY_MAX_K)
+            with self._code_lock:  # one attached column: attach and search as one step
+                n_bytes = self._attach_codes(binary_key)
+                if n_bytes == 0:
+                    return empty
+                for q in qs:
+                    if q.size != n_bytes:
+                        raise ValueError(f"the query's code holds {q.size} bytes, the stored codes {n_bytes}")
+                have = self._code_mask
+                mask = have if mask is None else (np.asarray(mask, np.uint32)[:have.size] & have)
+                dist, idx = self._index.search_hamming(np.stack(qs), fetch, mask=mask)
+            meta = self._metadata
+            out = []
+            if R is None:
+                for b in range(B):
+                    valid = idx[b] >= 0
+                    ib = idx[b][valid].tolist()
+                    out.append((ib, dist[b][valid].astype(np.int64).tolist(), [meta[i] if i < len(meta) else {} for i in ib]))
+                return out
+            # rescoring: the fetched ids, sorted, are each query's row list of the exact subset search
+            lists = [np.sort(idx[b][idx[b] >= 0]) for b in range(B)]
+            scores, ridx = self._index.search_rows(R, k, lists)
+            for b in range(B):
+                valid = ridx[b] >= 0
+                ib = ridx[b][valid].tolist()
+                d_of = dict(zip(idx[b].tolist(), dist[b].tolist()))
+                out.append((ib, [int(d_of[i]) for i in ib], [meta[i] if i < len(meta) else {} for i in ib],
+                            scores[b][valid].astype(np.float64).tolist()))
             return out
 
     # ---- sparse and hybrid query ----------------------------------------------------------
