@@ -162,7 +162,9 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * query of vdb_index_search_hybrid_sum, 0 = auto, 1..512; its stats "hybrid_sum_searches",
  * "hybrid_sum_queries" are described there) and "hamming_wgs" (workgroups per query block of
  * vdb_index_search_hamming, 0 = auto, 1..512; the code column's and its stats "code_rows",
- * "code_bytes", "code_sets", "hamming_searches", "hamming_queries" are described there).  The numeric columns and predicate masks have no
+ * "code_bytes", "code_sets", "hamming_searches", "hamming_queries" are described there) and
+ * "hamming_mfma" (which kernel that call takes: 0 = auto, 1 = the MFMA one whenever eligible, 2 =
+ * never; its stats "hamming_mfma_searches", "hamming_mfma_queries" are described there).  The numeric columns and predicate masks have no
  * knob; their stats "column_slots", "column_sets", "filter_calls", "filter_preds" are described at
  * vdb_index_filter_mask.  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
@@ -751,7 +753,16 @@ int32_t vdb_index_search_hybrid_sum(vdb_index* idx, const float* queries,
  * An empty index with an empty column attached gives "no result" everywhere.  Takes the shared lock.
  * Knob "hamming_wgs": workgroups per block of queries, 0 = auto, 1..512 (results identical).  Stats:
  * "hamming_searches", "hamming_queries" (cumulative over successful calls); "searches", "queries"
- * and every "searches_*" stat stay still. */
+ * and every "searches_*" stat stay still.
+ * Two kernels serve the call, with the same result in every byte: XOR + popcount per (row, query),
+ * and, for large batches, the int8 matrix instruction (stored bits as 0 / 1, query bits as -1 / +1,
+ * d = |q| - dot).  A call is eligible for the second when k <= 64, at every code
+ * width.  Knob "hamming_mfma": 0 = auto (the default: eligible calls of at least 64 queries take it),
+ * 1 = every eligible call takes it whatever the batch, 2 = never; any other value is
+ * VDB_ERR_INVALID.  A call that is not eligible runs the popcount kernel as before.  "hamming_wgs"
+ * means the same for both (a block is 64 queries for the second kernel).  Stats
+ * "hamming_mfma_searches", "hamming_mfma_queries": the calls and queries the second kernel served;
+ * "hamming_searches" / "hamming_queries" count both. */
 int32_t vdb_index_set_codes(vdb_index* idx, const uint8_t* codes, int64_t n, int32_t n_bytes,
                             int32_t mem, void* stream);
 int32_t vdb_index_search_hamming(vdb_index* idx, const uint8_t* queries, int32_t n_queries, int32_t k,

@@ -303,7 +303,9 @@ struct vdb_index {
     int32_t code_bytes = 0;
     bool code_set = false;
     int64_t hamming_wgs = 0;  // knob: workgroups per query block of a Hamming search (0 = auto)
+    int64_t hamming_mfma = 0;  // knob: the integer-MFMA form of it (0 = by the batch size, 1 = whenever eligible, 2 = never)
     std::atomic<int64_t> n_code_sets{0}, n_hamming_searches{0}, n_hamming_queries{0};
+    std::atomic<int64_t> n_hamming_mfma_searches{0}, n_hamming_mfma_queries{0};
     std::atomic<int64_t> n_hybrid_searches{0}, n_hybrid_queries{0};
     // vdb_index_search_hybrid_sum: calls and queries (successful calls)
     std::atomic<int64_t> n_hybsum_searches{0}, n_hybsum_queries{0};
@@ -1136,6 +1138,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "hamming_wgs must be in [0, %d] (0 = auto)", kHamMaxSeg);
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->hamming_wgs = value;
+    } else if (n == "hamming_mfma") {
+        if (value < 0 || value > 2)
+            return set_error(VDB_ERR_INVALID, "hamming_mfma must be 0 (auto), 1 (whenever eligible) or 2 (never)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->hamming_mfma = value;
     } else if (n == "hybrid_sum_wgs") {
         if (value < 0 || value > kHybsumMaxSeg)
             return set_error(VDB_ERR_INVALID, "hybrid_sum_wgs must be in [0, %d] (0 = auto)", kHybsumMaxSeg);
@@ -1302,6 +1309,8 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "code_sets") *value = ix->n_code_sets.load();
     else if (n == "hamming_searches") *value = ix->n_hamming_searches.load();
     else if (n == "hamming_queries") *value = ix->n_hamming_queries.load();
+    else if (n == "hamming_mfma_searches") *value = ix->n_hamming_mfma_searches.load();
+    else if (n == "hamming_mfma_queries") *value = ix->n_hamming_mfma_queries.load();
     else if (n == "hybrid_searches") *value = ix->n_hybrid_searches.load();
     else if (n == "hybrid_queries") *value = ix->n_hybrid_queries.load();
     else if (n == "hybrid_sum_searches") *value = ix->n_hybsum_searches.load();
@@ -3978,7 +3987,9 @@ int32_t vdb_index_search_hamming(vdb_index* ix, const uint8_t* queries, int32_t 
 
     const bool masked = row_mask != nullptr && N > 0;
     const int n_bytes = ix->code_bytes;
-    const int qb = ham_block(k, B);
+    // the form: the integer MFMA at large batches and small k, else popcount (vdb_hamming_plan.h)
+    const bool mfma = ham_use_mfma(ix->hamming_mfma, B, k, n_bytes);
+    const int qb = mfma ? ham_mfma_qb(k) : ham_block(k, B);
     const int n_blocks = ham_n_blocks(B, qb);
     const int n_seg = N > 0 ? ham_n_seg(ix->hamming_wgs, N, n_blocks, ix->n_cu) : 1;
     const HammingScratch sc = hamming_scratch(B, n_bytes, k, qb, n_seg, N, host, masked);
@@ -4017,7 +4028,10 @@ int32_t vdb_index_search_hamming(vdb_index* ix, const uint8_t* queries, int32_t 
     // the per-block counters start at zero (the kernel leaves them so; a grown workspace is fresh)
     if (n_seg > 1) HIP_TRY(hipMemsetAsync(a.done, 0, (size_t)n_blocks * sizeof(int), st));
     // (an empty index: no row is read, every slot "no result")
-    HIP_TRY(launch_hamming_search(a, qb, n_seg, st));
+    if (mfma)
+        HIP_TRY(launch_hamming_mfma(a, n_seg, st));
+    else
+        HIP_TRY(launch_hamming_search(a, qb, n_seg, st));
     if (host) {
         const char* r = nullptr;
         rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
@@ -4027,6 +4041,10 @@ int32_t vdb_index_search_hamming(vdb_index* ix, const uint8_t* queries, int32_t 
     }
     ix->n_hamming_searches++;
     ix->n_hamming_queries += B;
+    if (mfma) {
+        ix->n_hamming_mfma_searches++;
+        ix->n_hamming_mfma_queries += B;
+    }
     return VDB_OK;
 }
 

@@ -34,6 +34,7 @@
 #include "vdb_internal.h"
 #include "vdb_merge_block.h"
 #include "vdb_hamming_plan.h"
+#include "vdb_hamming_tail.h"
 
 namespace vdb {
 
@@ -66,13 +67,6 @@ hipError_t launch_hamming_pack(const uint8_t* codes, int64_t n, int n_bytes, uin
 }
 
 // ---- the search -------------------------------------------------------------------------------
-__device__ __forceinline__ void hamming_write(const HammingArgs& a, int b, int e, float key, uint32_t r) {
-    const bool valid = r != 0xFFFFFFFFu;
-    const size_t o = (size_t)b * a.k + e;
-    a.out_d[o] = valid ? (int32_t)(-key) : -1;
-    a.out_i[o] = valid ? (int64_t)((uint64_t)r + (uint64_t)a.index_offset) : (int64_t)-1;
-}
-
 template <int QB>
 __global__ void __launch_bounds__(256) hamming_kernel(HammingArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -1,7 +1,9 @@
 // vdb_hamming_plan.h — the host arithmetic of vdb_index_set_codes and vdb_index_search_hamming
 // (vdb_api.cpp) and the decisions their kernels share with it (vdb_hamming.hip): the limits, the
 // tiled layout of the code column, the query-block size QB, how the tiles are dealt to workgroups
-// and waves, the LDS layout, the per-call scratch and the validation (one enum value per cause).
+// and waves, the LDS layout, the per-call scratch and the validation (one enum value per cause); and
+// for the integer-MFMA form of the search (vdb_hamming_mfma.hip): its bit-to-operand mapping, block
+// size, k limit, LDS layout and the choice between the two forms (ham_use_mfma).
 // Plain C++ with no HIP in it, so a stand-alone CPU program can sweep it under a sanitizer
 // (tools/hamming_plan_check.cpp).
 #pragma once
@@ -138,6 +140,72 @@ inline int ham_n_seg(int64_t knob, int64_t N, int n_blocks, int n_cu) {
 // The mask words of a tile: rows [64 t, 64 t + 64) are bits of words 2 t and 2 t + 1; the second may
 // lie past the mask's ceil(N / 32) words (it then counts as zero: its rows are past N).
 VDB_HAM_HD inline int64_t ham_mask_words(int64_t N) { return (N + 31) / 32; }
+
+// ---- the integer-MFMA form (vdb_hamming_mfma.hip) ---------------------------------------------------
+// The same call, column and result through v_mfma_i32_32x32x32_i8: a stored bit x becomes the int8
+// 0 / 1, a query bit q becomes -1 / +1, and dot = 2 (q.x) - |x|, so the distance is |q| - dot.  A
+// workgroup (4 waves) takes a block of kHamMfmaQB queries (two MFMA query tiles); per trip wave w
+// takes tile 4 c + w as two 32-row sub-tiles, as the popcount form deals them.
+constexpr int kHamMfmaQT = 2;                        // query tiles of 32 per workgroup
+constexpr int kHamMfmaQB = 32 * kHamMfmaQT;
+constexpr int kHamMfmaMaxK = 64;
+// A query's candidate buffer, shared by the four waves: kHamMfmaCap (distance, row) entries.  A wave
+// offers at most 64 rows per query and trip, so after a compaction to k <= kHamMfmaMaxK entries one
+// wave's offers always fit; above kHamMfmaHigh entries a buffer is compacted at the trip's end.
+constexpr int kHamMfmaCap = 128;
+constexpr int kHamMfmaHigh = 96;
+static_assert(kHamMfmaMaxK + kHamTileRows <= kHamMfmaCap, "one wave's offers fit a compacted buffer");
+// The smallest batch that takes this form by itself (knob "hamming_mfma" = 0).  Measured, DESIGN.md §24.
+constexpr int kHamMfmaMinQueries = 64;
+
+// The bit mapping.  One MFMA multiplies 32 code bits: lane half h supplies 16 bytes.  Code bit b (bit
+// b % 64 of word b / 64) goes to MFMA step 4 (word / 2) + (b % 64) / 16, lane half word % 2, byte b % 16:
+// lane l of step s reads word ham_mfma_word(s, l / 32) and expands its 16 bits from ham_mfma_shift(s)
+// up, bit i to byte i.  The same function serves rows and queries; a dot product needs no more.
+struct HamMfmaSlot { int step, half, byte; };
+VDB_HAM_HD inline HamMfmaSlot ham_mfma_slot(int bit) {
+    const int w = bit / 64, c = bit % 64;
+    return HamMfmaSlot{4 * (w / 2) + c / 16, w % 2, c % 16};
+}
+VDB_HAM_HD inline int ham_mfma_word(int step, int half) { return 2 * (step / 4) + half; }
+VDB_HAM_HD inline int ham_mfma_shift(int step) { return 16 * (step % 4); }
+VDB_HAM_HD inline int ham_mfma_words(int W) { return (W + 1) / 2 * 2; }   // W up to a whole word pair (the odd one: zero)
+VDB_HAM_HD inline int ham_mfma_steps(int W) { return 2 * ham_mfma_words(W); }
+// Four bits to the four bytes of an operand register: a row's 0 / 1 (the products of the multiply do
+// not overlap: bit i lands on bit 8 i) and a query's -1 / +1.
+VDB_HAM_HD inline uint32_t ham_mfma_row4(uint32_t nib) { return ((nib & 15u) * 0x00204081u) & 0x01010101u; }
+VDB_HAM_HD inline uint32_t ham_mfma_query4(uint32_t nib) {
+    const uint32_t e = ham_mfma_row4(nib);
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(0x000001FFu, 0x000001FFu, e);  // selector byte 0 -> 0xFF, 1 -> 0x01
+#else
+    const uint32_t ne = e ^ 0x01010101u;
+    return e | ((ne << 8) - ne);
+#endif
+}
+// LDS of a workgroup (bytes): the block's query words word-major [ham_mfma_words(W)][QB] (a lane's
+// read of "word w of query l % 32" is conflict free), the candidate buffers [QB][cap] of 64-bit keys
+// (distance << 32 | row), the thresholds [QB] and the counts [QB].  (The segments' lists are merged
+// by a launch of its own, one workgroup per query, with the merge's buffer as its only LDS.)
+VDB_HAM_HD inline int64_t ham_mfma_query_lds(int W) { return (int64_t)ham_mfma_words(W) * kHamMfmaQB * 8; }
+VDB_HAM_HD inline int64_t ham_mfma_cand_off(int W) { return ham_mfma_query_lds(W); }
+VDB_HAM_HD inline int64_t ham_mfma_thr_off(int W) { return ham_mfma_cand_off(W) + (int64_t)kHamMfmaQB * kHamMfmaCap * 8; }
+VDB_HAM_HD inline int64_t ham_mfma_cnt_off(int W) { return ham_mfma_thr_off(W) + (int64_t)kHamMfmaQB * 8; }
+VDB_HAM_HD inline int64_t ham_mfma_lds_bytes(int W) { return ham_mfma_cnt_off(W) + (int64_t)kHamMfmaQB * 4; }
+// The kernel's static LDS (its flag words) on top of that: room kept under the limit.
+constexpr int64_t kHamMfmaStaticLds = 256;
+// The query block of this form for k, 0 = k is not served.  Every width fits with kHamMfmaQB:
+// 64 KiB of queries at the longest code and 64 KiB of candidates.
+VDB_HAM_HD inline int ham_mfma_qb(int k) {
+    if (k < 1 || k > kHamMfmaMaxK) return 0;
+    return ham_mfma_lds_bytes(kHamMaxWords) + kHamMfmaStaticLds <= kHamLdsLimit ? kHamMfmaQB : 0;
+}
+// Which form a call takes.  knob ("hamming_mfma"): 0 = by the batch size, 1 = this form whenever the
+// call is eligible, 2 = never.  Every code width is eligible.
+VDB_HAM_HD inline bool ham_use_mfma(int64_t knob, int n_queries, int k, int n_bytes) {
+    if (knob == 2 || ham_mfma_qb(k) == 0 || n_bytes < 1 || n_bytes > kHamMaxBytes || n_queries < 1) return false;
+    return knob == 1 || n_queries >= kHamMfmaMinQueries;
+}
 
 // ---- scratch ------------------------------------------------------------------------------------------
 inline int64_t ham_align(int64_t b) { return (b + 255) / 256 * 256; }

@@ -492,6 +492,12 @@ struct HammingArgs {
 };
 size_t hamming_search_lds_bytes(int qb, int W, int KE, int n_seg);
 hipError_t launch_hamming_search(const HammingArgs& a, int qb, int n_seg, hipStream_t st);
+// The same search through the integer MFMA (vdb_hamming_mfma.hip): the same arguments, lists and
+// results; grid (n_seg, blocks of kHamMfmaQB queries); k <= kHamMfmaMaxK (ham_mfma_qb(k) != 0).  With
+// more than one live segment a second launch merges the lists, one workgroup per query; done is not
+// used and stays zero.
+size_t hamming_mfma_lds_bytes(int W);
+hipError_t launch_hamming_mfma(const HammingArgs& a, int n_seg, hipStream_t st);
 
 // Weighted-sum hybrid search (vdb_hybsum.hip, vdb_index_search_hybrid_sum).  Query b is the dense
 // vector Q[b] (qn64[b]: its canonical norm) and the sparse entries [q_indptr[b], q_indptr[b + 1]) of

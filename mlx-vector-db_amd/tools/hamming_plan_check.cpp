@@ -3,7 +3,7 @@
 // of tiles to segments and waves (every row exactly once), the tile / word / lane address of a row's
 // byte (a packed column restated from it gives the naive distances), the LDS layout (disjoint,
 // inside the budget), the validation causes and the scratch layout (aligned, disjoint, inside the
-// total).  A stand-alone host program (its own main, no GPU, nothing loaded into another process);
+// total), and the integer-MFMA form's bit mapping, operands, LDS layout and eligibility.  A stand-alone host program (its own main, no GPU, nothing loaded into another process);
 // `make hamming-plan-check` builds it with -fsanitize=address,undefined and runs it.
 #include <algorithm>
 #include <cstdint>
@@ -254,6 +254,91 @@ static void check_scratch() {
                         }
 }
 
+// The integer-MFMA form: the bit-to-slot mapping is a bijection and agrees with what a lane reads and
+// expands, the operands give the distance by |q| - dot, the LDS layout is disjoint and inside the
+// budget, and ham_use_mfma decides as stated at every boundary.
+static void check_mfma() {
+    std::mt19937 rng(11);
+    for (int n_bytes : {1, 3, 4, 5, 8, 9, 16, 24, 136, 1023, 1024}) {
+        const int W = ham_words(n_bytes), steps = ham_mfma_steps(W);
+        CHECK(ham_mfma_words(W) == W + W % 2 && steps == 4 * ((W + 1) / 2), "steps of W %d", W);
+        // every bit (pad bits of the last word included) lands in exactly one (step, half, byte) slot
+        std::vector<int> hit((size_t)steps * 32, 0);
+        for (int bit = 0; bit < 64 * W; ++bit) {
+            const HamMfmaSlot sl = ham_mfma_slot(bit);
+            CHECK(sl.step >= 0 && sl.step < steps && (sl.half == 0 || sl.half == 1) && sl.byte >= 0 && sl.byte < 16, "slot of bit %d", bit);
+            ++hit[(size_t)(sl.step * 2 + sl.half) * 16 + sl.byte];
+            // and it is where a lane of that half finds it: word, shift and byte of the expansion
+            CHECK(ham_mfma_word(sl.step, sl.half) == bit / 64 && ham_mfma_shift(sl.step) + sl.byte == bit % 64, "read of bit %d", bit);
+        }
+        int used = 0;
+        for (int h : hit) {
+            CHECK(h <= 1, "a slot taken twice");
+            used += h;
+        }
+        CHECK(used == 64 * W, "slots used");
+        for (int st = 0; st < steps; ++st)
+            for (int h = 0; h < 2; ++h) CHECK(ham_mfma_word(st, h) < ham_mfma_words(W), "a word past the padded row");
+        // the operands: rows 0 / 1, queries -1 / +1, distance = |q| - dot, the missing pair word zero
+        for (int rep = 0; rep < 4; ++rep) {
+            std::vector<uint8_t> x((size_t)n_bytes), q((size_t)n_bytes);
+            for (auto& b : x) b = rep == 1 ? 0xFF : rep == 2 ? 0 : (uint8_t)rng();
+            for (auto& b : q) b = rep == 1 ? 0 : rep == 2 ? 0xFF : (uint8_t)rng();
+            int dot = 0, qpop = 0;
+            for (int w = 0; w < W; ++w) qpop += __builtin_popcountll(ham_word_of(q.data(), n_bytes, w));
+            for (int st = 0; st < steps; ++st)
+                for (int h = 0; h < 2; ++h) {
+                    const int w = ham_mfma_word(st, h);
+                    const uint64_t xw = w < W ? ham_word_of(x.data(), n_bytes, w) : 0ull;
+                    const uint64_t qw = w < W ? ham_word_of(q.data(), n_bytes, w) : 0ull;
+                    for (int d = 0; d < 4; ++d) {
+                        const uint32_t xe = ham_mfma_row4((uint32_t)(xw >> (ham_mfma_shift(st) + 4 * d)));
+                        const uint32_t qe = ham_mfma_query4((uint32_t)(qw >> (ham_mfma_shift(st) + 4 * d)));
+                        for (int i = 0; i < 4; ++i) {
+                            const int xb = (int8_t)(xe >> (8 * i)), qb = (int8_t)(qe >> (8 * i));
+                            const int bit = ham_mfma_shift(st) + 4 * d + i;
+                            CHECK(xb == (int)((xw >> bit) & 1) && qb == 2 * (int)((qw >> bit) & 1) - 1, "expansion of bit %d", bit);
+                            dot += xb * qb;
+                        }
+                    }
+                }
+            CHECK(qpop - dot == naive_distance(x.data(), q.data(), n_bytes), "distance by the dot product, %d bytes", n_bytes);
+            CHECK(dot >= -8192 && dot <= 8192, "dot range");
+        }
+    }
+    // eligibility and LDS
+    CHECK(kHamMfmaMinQueries >= 32, "the auto threshold");
+    for (int k = 1; k <= kHamMaxK; ++k) {
+        const int qb = ham_mfma_qb(k);
+        CHECK(qb == (k <= kHamMfmaMaxK ? kHamMfmaQB : 0), "mfma QB of k %d", k);
+        if (!qb) continue;
+        CHECK(ham_merge_lds(ham_ke(k)) <= 64 * 1024, "the merge launch's LDS needs no opt-in");
+        CHECK(k + kHamTileRows <= kHamMfmaCap && kHamMfmaHigh < kHamMfmaCap, "one wave's offers fit");
+    }
+    CHECK(ham_mfma_qb(10) == 64 && ham_mfma_qb(0) == 0, "k = 10 is served");
+    for (int W = 1; W <= kHamMaxWords; ++W) {
+        std::vector<std::pair<int64_t, int64_t>> spans;
+        spans.push_back({0, ham_mfma_query_lds(W)});
+        for (int q = 0; q < kHamMfmaQB; ++q) spans.push_back({ham_mfma_cand_off(W) + (int64_t)q * kHamMfmaCap * 8, ham_mfma_cand_off(W) + (int64_t)(q + 1) * kHamMfmaCap * 8});
+        spans.push_back({ham_mfma_thr_off(W), ham_mfma_thr_off(W) + kHamMfmaQB * 8});
+        spans.push_back({ham_mfma_cnt_off(W), ham_mfma_cnt_off(W) + kHamMfmaQB * 4});
+        std::sort(spans.begin(), spans.end());
+        CHECK(spans.front().first == 0 && spans.back().second == ham_mfma_lds_bytes(W), "mfma LDS extent W %d", W);
+        for (size_t i = 0; i + 1 < spans.size(); ++i) CHECK(spans[i].second == spans[i + 1].first, "mfma LDS overlap or gap");
+        for (auto& sp : spans) CHECK(sp.first % 8 == 0, "mfma LDS alignment");
+        CHECK(ham_mfma_query_lds(W) == (int64_t)(W + W % 2) * 64 * 8, "query words of W %d", W);
+        CHECK(ham_mfma_lds_bytes(W) + kHamMfmaStaticLds <= 160 * 1024, "mfma LDS limit W %d", W);
+    }
+    for (int64_t knob : {0, 1, 2})
+        for (int B : {1, 31, 32, kHamMfmaMinQueries - 1, kHamMfmaMinQueries, kHamMfmaMinQueries + 1, 1024, kHamMaxQueries})
+            for (int k : {1, 10, kHamMfmaMaxK, kHamMfmaMaxK + 1, 1024})
+                for (int n_bytes : {1, 24, 1024}) {
+                    const bool want = knob != 2 && k <= kHamMfmaMaxK && (knob == 1 || B >= kHamMfmaMinQueries);
+                    CHECK(ham_use_mfma(knob, B, k, n_bytes) == want, "use_mfma knob %lld B %d k %d", (long long)knob, B, k);
+                }
+    CHECK(!ham_use_mfma(1, 0, 10, 8) && !ham_use_mfma(1, 64, 10, 0) && !ham_use_mfma(1, 64, 10, 1025), "degenerate calls");
+}
+
 int main() {
     check_qb();
     check_deal();
@@ -261,6 +346,7 @@ int main() {
     check_lds();
     check_validation();
     check_scratch();
+    check_mfma();
     std::printf("hamming plan ok: %ld checks\n", g_checks);
     return 0;
 }
