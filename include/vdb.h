@@ -158,7 +158,10 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "maxsim_sets", "maxsim_bad_sets", "maxsim_skipped_rows") and "sparse_wgs" (workgroups per query
  * of vdb_index_search_sparse, 0 = auto; the sparse and hybrid calls' stats "sparse_rows",
  * "sparse_nnz", "sparse_sets", "sparse_searches", "sparse_queries", "sparse_bad_queries",
- * "hybrid_searches", "hybrid_queries" are described there) and "hybrid_sum_wgs" (workgroups per
+ * "hybrid_searches", "hybrid_queries" are described there) and "sparse_inverted" (which kernel
+ * that call and the hybrid call's sparse list take: 0 = auto, 1 = the inverted one whenever postings
+ * exist, 2 = never, and vdb_index_set_sparse then builds none; its stats "sparse_inverted_built",
+ * "sparse_inverted_searches", "sparse_inverted_queries" are described there) and "hybrid_sum_wgs" (workgroups per
  * query of vdb_index_search_hybrid_sum, 0 = auto, 1..512; its stats "hybrid_sum_searches",
  * "hybrid_sum_queries" are described there) and "hamming_wgs" (workgroups per query block of
  * vdb_index_search_hamming, 0 = auto, 1..512; the code column's and its stats "code_rows",
@@ -629,6 +632,17 @@ int32_t vdb_index_search_fused(vdb_index* idx, const float* queries, int32_t n_s
  * vdb_index_search_rows does.  Knob "sparse_wgs": workgroups per query, 0 = auto (results identical).
  * Stats: "sparse_searches", "sparse_queries", "sparse_bad_queries"; "searches" / "queries" and every
  * "searches_*" stat stay still.
+ * Two kernels serve this call and the sparse list of vdb_index_search_hybrid with the same result in
+ * every byte: one walks every row's entries, the other (the inverted one) walks the postings of the
+ * query's terms, a term-major copy of the column in (term, row) order.
+ * vdb_index_set_sparse builds the postings on the device beside the CSR copy when n_terms <= 2^22 and
+ * the knob "sparse_inverted" is not 2; they take 8 (n_terms + 1) + 8 nnz bytes, counted in
+ * "device_bytes", and live and die with the column (a failed vdb_index_set_sparse leaves the earlier
+ * column and its postings).  Knob "sparse_inverted": 0 = auto (the default: the inverted kernel when
+ * postings exist and the index has at least 1 000 000 rows), 1 = whenever postings exist, 2 = never;
+ * another value -> VDB_ERR_INVALID.  Stats: "sparse_inverted_built" (0 / 1: the attached column has
+ * postings), "sparse_inverted_searches", "sparse_inverted_queries" (the calls and queries the inverted
+ * kernel served, hybrid calls included); every other stat moves as it does without it.
  *
  * vdb_index_search_hybrid: query b is the fused-search set whose list 0 is what vdb_index_search
  * returns for queries[b] with k = fetch_k and row_mask, whose list 1 is what vdb_index_search_sparse

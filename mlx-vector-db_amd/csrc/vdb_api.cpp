@@ -32,6 +32,7 @@
 #include "vdb_fuse_plan.h"
 #include "vdb_maxsim_plan.h"
 #include "vdb_sparse_plan.h"
+#include "vdb_sparse_inv_plan.h"
 #include "vdb_hamming_plan.h"
 #include "vdb_hybsum_plan.h"
 #include "vdb_recommend_plan.h"
@@ -292,6 +293,16 @@ struct vdb_index {
     int32_t sparse_terms = 0;
     bool sparse_set = false;
     int64_t sparse_wgs = 0;  // knob: workgroups per query of a sparse search (0 = auto)
+    // the column's postings, its term-major copy for the inverted kernel (vdb_sparse_inv_plan.h):
+    // inv_tptr [sparse_terms + 1] and inv_posts [sparse_nnz] in (term, row) order, built by
+    // vdb_index_set_sparse beside the CSR copy; they live and die with the column (inv_built says
+    // that the attached column has them, inv_bytes what they occupy)
+    int64_t* inv_tptr = nullptr;
+    SparsePost* inv_posts = nullptr;
+    bool inv_built = false;
+    int64_t inv_bytes = 0;
+    int64_t sparse_inverted = 0;  // knob: 0 = by the row count, 1 = whenever postings exist, 2 = never (and attach builds none)
+    std::atomic<int64_t> n_sparse_inv_searches{0}, n_sparse_inv_queries{0};
     // vdb_index_search_sparse / _hybrid: calls and queries (successful calls); the queries the sparse
     // kernel found bad are counted on the device (d_xmax + kSparseBadWord)
     std::atomic<int64_t> n_sparse_sets{0}, n_sparse_searches{0}, n_sparse_queries{0};
@@ -992,6 +1003,8 @@ int32_t vdb_index_destroy(vdb_index* ix) {
     if (ix->d_group_fb) (void)hipFree(ix->d_group_fb);
     if (ix->sparse_indptr) (void)hipFree(ix->sparse_indptr);
     if (ix->sparse_pairs) (void)hipFree(ix->sparse_pairs);
+    if (ix->inv_tptr) (void)hipFree(ix->inv_tptr);
+    if (ix->inv_posts) (void)hipFree(ix->inv_posts);
     if (ix->codes) (void)hipFree(ix->codes);
     for (int s = 0; s < kFilterSlots; ++s)
         if (ix->cols[s]) (void)hipFree(ix->cols[s]);
@@ -1133,6 +1146,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "sparse_wgs must be in [0, %d] (0 = auto)", kSparseMaxSeg);
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->sparse_wgs = value;
+    } else if (n == "sparse_inverted") {
+        if (!sparse_inv_knob_ok(value))
+            return set_error(VDB_ERR_INVALID, "sparse_inverted must be 0 (auto), 1 (whenever postings exist) or 2 (never)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->sparse_inverted = value;
     } else if (n == "hamming_wgs") {
         if (value < 0 || value > kHamMaxSeg)
             return set_error(VDB_ERR_INVALID, "hamming_wgs must be in [0, %d] (0 = auto)", kHamMaxSeg);
@@ -1248,7 +1266,8 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
         int64_t cb = 0;  // the numeric columns (vdb_index_set_column), attached or kept for the next attach
         for (int s = 0; s < kFilterSlots; ++s) cb += ix->cols[s] ? ix->col_cap[s] * 8 : 0;
         cb += ix->codes ? ix->code_cap_words * 8 : 0;  // the code column (vdb_index_set_codes), likewise
-        *value = xb + (xs_ptr(ix) ? xb : 0) + (ix->Xq ? xb / 2 : 0) + (ix->Xh ? xb / 4 : 0) + ix->cap_rows * 20 + cb;
+        *value = xb + (xs_ptr(ix) ? xb : 0) + (ix->Xq ? xb / 2 : 0) + (ix->Xh ? xb / 4 : 0) + ix->cap_rows * 20 + cb +
+                 (ix->inv_tptr ? ix->inv_bytes : 0);  // the sparse column's postings (vdb_index_set_sparse)
     } else if (n == "split_copy") *value = xs_ptr(ix) ? 1 : 0;
     else if (n == "split_copy_builds") *value = ix->n_xs_builds.load();
     else if (n == "rows_removed") *value = ix->n_rows_removed.load();
@@ -1304,6 +1323,9 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "sparse_sets") *value = ix->n_sparse_sets.load();
     else if (n == "sparse_searches") *value = ix->n_sparse_searches.load();
     else if (n == "sparse_queries") *value = ix->n_sparse_queries.load();
+    else if (n == "sparse_inverted_built") *value = ix->sparse_set && ix->inv_built ? 1 : 0;
+    else if (n == "sparse_inverted_searches") *value = ix->n_sparse_inv_searches.load();
+    else if (n == "sparse_inverted_queries") *value = ix->n_sparse_inv_queries.load();
     else if (n == "code_rows") *value = ix->code_set ? ix->code_n : 0;
     else if (n == "code_bytes") *value = ix->code_set ? ix->code_bytes : 0;
     else if (n == "code_sets") *value = ix->n_code_sets.load();
@@ -3487,14 +3509,34 @@ int32_t vdb_index_set_sparse(vdb_index* ix, const int64_t* indptr, const int32_t
         HIP_TRY(hipStreamSynchronize(st));
         return VDB_OK;
     };
-    const int rc = build();
+    // the postings, from the device CSR copy, after validation has passed and before the swap
+    int64_t* tptr_new = nullptr;
+    SparsePost* posts_new = nullptr;
+    const bool inv = sparse_inv_builds(ix->sparse_inverted, n_terms);
+    const auto build_postings = [&]() -> int {
+        if (!inv) return VDB_OK;
+        HIP_TRY(hipMalloc(&tptr_new, ((size_t)n_terms + 1) * sizeof(int64_t)));
+        HIP_TRY(hipMalloc(&posts_new, (size_t)std::max<int64_t>(nnz, 1) * sizeof(SparsePost)));
+        HIP_TRY(launch_sparse_inv_build(ind_new, pairs_new, n, nnz, n_terms, tptr_new, posts_new, st));
+        return VDB_OK;
+    };
+    int rc = build();
+    if (!rc) rc = build_postings();
     if (rc) {
         (void)hipFree(ind_new);
         (void)hipFree(pairs_new);
+        if (tptr_new) (void)hipFree(tptr_new);
+        if (posts_new) (void)hipFree(posts_new);
         return rc;
     }
     if (ix->sparse_indptr) (void)hipFree(ix->sparse_indptr);
     if (ix->sparse_pairs) (void)hipFree(ix->sparse_pairs);
+    if (ix->inv_tptr) (void)hipFree(ix->inv_tptr);
+    if (ix->inv_posts) (void)hipFree(ix->inv_posts);
+    ix->inv_tptr = tptr_new;
+    ix->inv_posts = posts_new;
+    ix->inv_built = inv;
+    ix->inv_bytes = inv ? ((int64_t)n_terms + 1) * 8 + std::max<int64_t>(nnz, 1) * 8 : 0;
     ix->sparse_indptr = ind_new;
     ix->sparse_pairs = pairs_new;
     ix->sparse_n = n;
@@ -3506,6 +3548,15 @@ int32_t vdb_index_set_sparse(vdb_index* ix, const int64_t* indptr, const int32_t
 }
 
 namespace {
+// The sparse search of vdb_index_search_sparse / _hybrid by one of its two kernels (the same result
+// in every byte): the inverted one when the attached column has postings and the knob
+// "sparse_inverted" or the row count says so (vdb_sparse_inv_plan.h); *inverted: which one ran.
+hipError_t launch_sparse_either(vdb_index* ix, const SparseArgs& a, int n_queries, int n_seg, hipStream_t st,
+                                bool* inverted) {
+    *inverted = sparse_inv_serves(ix->sparse_inverted, ix->sparse_set && ix->inv_built, a.N);
+    return *inverted ? launch_sparse_inv_search(a, ix->inv_tptr, ix->inv_posts, n_queries, n_seg, st)
+                     : launch_sparse_search(a, n_queries, n_seg, st);
+}
 // What a sparse or hybrid call's validation found, as the error the call returns.
 int sparse_call_error(int cause, int k, int fetch_k, int64_t at) {
     switch (cause) {
@@ -3609,7 +3660,8 @@ int32_t vdb_index_search_sparse(vdb_index* ix, const int64_t* q_indptr, const in
     // the per-query counters start at zero (the kernel leaves them so; a grown workspace is fresh)
     if (n_seg > 1) HIP_TRY(hipMemsetAsync(a.done, 0, (size_t)B * sizeof(int), st));
     // (an empty index: no row is read, every slot "no result"; a device call's bad queries still count)
-    HIP_TRY(launch_sparse_search(a, B, n_seg, st));
+    bool inverted = false;
+    HIP_TRY(launch_sparse_either(ix, a, B, n_seg, st, &inverted));
     if (host) {
         const char* r = nullptr;
         rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
@@ -3620,6 +3672,10 @@ int32_t vdb_index_search_sparse(vdb_index* ix, const int64_t* q_indptr, const in
     }
     ix->n_sparse_searches++;
     ix->n_sparse_queries += B;
+    if (inverted) {
+        ix->n_sparse_inv_searches++;
+        ix->n_sparse_inv_queries += B;
+    }
     return VDB_OK;
 }
 
@@ -3742,7 +3798,8 @@ int32_t vdb_index_search_hybrid(vdb_index* ix, const float* queries, const int64
     sa.bad = ix->d_xmax + kSparseBadWord;
     sa.index_offset = 0;
     if (n_seg > 1) HIP_TRY(hipMemsetAsync(sa.done, 0, (size_t)B * sizeof(int), st));
-    HIP_TRY(launch_sparse_search(sa, B, n_seg, st));
+    bool inverted = false;
+    HIP_TRY(launch_sparse_either(ix, sa, B, n_seg, st, &inverted));
     // step 4: one workgroup per query fuses its two lists by weighted reciprocal rank
     HIP_TRY(launch_hybrid_sets(offs, wts, B, w_dense, w_sparse, st));
     a.fs = fs; a.fi = fi; a.fk = fk;
@@ -3766,6 +3823,10 @@ int32_t vdb_index_search_hybrid(vdb_index* ix, const float* queries, const int64
     }
     ix->n_hybrid_searches++;
     ix->n_hybrid_queries += B;
+    if (inverted) {
+        ix->n_sparse_inv_searches++;
+        ix->n_sparse_inv_queries += B;
+    }
     return VDB_OK;
 }
 

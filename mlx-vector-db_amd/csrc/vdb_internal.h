@@ -468,6 +468,16 @@ struct SparseArgs {
 };
 size_t sparse_search_lds_bytes(int KE, int n_seg);
 hipError_t launch_sparse_search(const SparseArgs& a, int n_queries, int n_seg, hipStream_t st);
+// The inverted (term-major) form of the same search (vdb_sparse_inv.hip): the same arguments, scratch
+// and results in every byte; it reads the postings tptr [n_terms + 1] / posts [nnz] in (term, row)
+// order instead of a.indptr / a.pairs.  Build: the postings of the device CSR column indptr [n + 1] /
+// pairs [nnz] into tptr / posts, complete on return (temporaries are allocated and freed inside).
+struct SparsePost;
+hipError_t launch_sparse_inv_build(const int64_t* indptr, const SparsePair* pairs, int64_t n, int64_t nnz, int32_t n_terms,
+                                   int64_t* tptr, SparsePost* posts, hipStream_t st);
+size_t sparse_inv_search_lds_bytes(int KE, int n_seg);
+hipError_t launch_sparse_inv_search(const SparseArgs& a, const int64_t* tptr, const SparsePost* posts, int n_queries,
+                                    int n_seg, hipStream_t st);
 // The hybrid call's sets for the fuse kernel: offs [n_queries + 1] = 0, 2, 4, ... and weights
 // [2 n_queries] = (w_dense, w_sparse) per set, written on the device.
 hipError_t launch_hybrid_sets(int64_t* offs, double* weights, int n_queries, double w_dense, double w_sparse,

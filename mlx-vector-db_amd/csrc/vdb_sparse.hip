@@ -19,11 +19,14 @@
 // Device-memory calls are not validated on the host, so the kernel takes any query: offsets are
 // clamped to [0, q_nnz], and a query whose range is bad or that holds a term id out of range or not
 // above its predecessor, or a non-finite weight, gives "no result" in every slot and is counted in
-// *bad.  The column itself was validated when it was attached.
+// *bad.  The column itself was validated when it was attached.  Query handling and the tail are in
+// vdb_sparse_query.h, shared with the inverted (term-major) form of this search (vdb_sparse_inv.hip),
+// which gives the same result in every byte.
 #include "vdb_common.h"
 #include "vdb_internal.h"
 #include "vdb_merge_block.h"
 #include "vdb_sparse_plan.h"
+#include "vdb_sparse_query.h"
 
 namespace vdb {
 
@@ -78,14 +81,6 @@ hipError_t launch_sparse_pack(const int32_t* terms, const float* weights, int64_
 }
 
 // ---- the search -------------------------------------------------------------------------------
-__device__ __forceinline__ void sparse_write(const SparseArgs& a, int b, int e, double key, uint32_t r) {
-    const bool valid = r != 0xFFFFFFFFu;
-    const size_t o = (size_t)b * a.out_ld + e;
-    // (metric 0 of write_result: the score is (float)key, round to nearest even)
-    write_result(0, key, valid ? (uint64_t)r + (uint64_t)a.index_offset : 0, valid, a.out_s + o, a.out_i + o,
-                 a.out_k ? a.out_k + o : nullptr);
-}
-
 __global__ void __launch_bounds__(256) sparse_kernel(SparseArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int KE = a.KE;
@@ -101,33 +96,19 @@ __global__ void __launch_bounds__(256) sparse_kernel(SparseArgs a) {
     char* tkmem = smem + kSparseQueryLds;
     double* kbase = reinterpret_cast<double*>(tkmem);
     uint32_t* ibase = reinterpret_cast<uint32_t*>(tkmem + (size_t)kSparseWaves * cap * sizeof(double));
-    double* bk = kbase + (size_t)wv * cap;
-    uint32_t* bi = ibase + (size_t)wv * cap;
 
-    // this query's entries (every workgroup of the query reads and judges them alike)
-    const SparseQRange rg = sparse_query_range(a.q_indptr[b], a.q_indptr[b + 1], a.q_nnz);
-    const int len = rg.len;
-    bool bad_e = false;
-    for (int e = threadIdx.x; e < len; e += 256) {
-        const int32_t t = a.q_terms[rg.o0 + e];
-        const int32_t prev = e > 0 ? a.q_terms[rg.o0 + e - 1] : -1;
-        const float w = a.q_weights[rg.o0 + e];
-        bad_e = bad_e || !sparse_term_ok(t, prev, a.n_terms) || !sparse_weight_ok(w);
-        qt[e] = t;
-        qw[e] = w;
-    }
-    const bool bad = __syncthreads_or(bad_e ? 1 : 0) != 0 || rg.bad;  // (also: the query is in LDS)
-    if (bad && s == 0 && threadIdx.x == 0 && a.bad) atomicAdd(a.bad, 1ull);
+    // this query's entries, loaded and judged (vdb_sparse_query.h)
+    bool bad;
+    const int len = sparse_load_query(a, b, s, qt, qw, &bad);
     const int live = (bad || len == 0) ? 0 : sparse_live_segs(a.N, n_seg);
     if (live == 0) {  // a bad query, one without terms, or no rows: "no result" in every slot
-        if (s == 0)
-            for (int e = threadIdx.x; e < a.k; e += 256) sparse_write(a, b, e, -INFINITY, 0xFFFFFFFFu);
+        if (s == 0) sparse_fill_none(a, b);
         return;
     }
     if (s >= live) return;  // more segments than chunks: nothing to do, and not counted below
 
     WaveTopK<double, uint32_t> tk;
-    tk.init(bk, bi, KE);
+    tk.init(kbase + (size_t)wv * cap, ibase + (size_t)wv * cap, KE);
     const int64_t n_chunks = sparse_n_chunks(a.N);
     for (int64_t c = s; c < n_chunks; c += n_seg) {
         const int64_t row = sparse_row_of(c, wv, lane);
@@ -149,47 +130,8 @@ __global__ void __launch_bounds__(256) sparse_kernel(SparseArgs a) {
         }
         tk.offer(in && matched, acc, in ? (uint32_t)row : 0xFFFFFFFFu);
     }
-    tk.finish();
-    __syncthreads();
-    if (wv == 0) {
-        for (int w = 1; w < kSparseWaves; ++w) {
-            const double* ok = kbase + (size_t)w * cap;
-            const uint32_t* oi = ibase + (size_t)w * cap;
-            for (int e0 = 0; e0 < KE; e0 += 64) {
-                const int e = e0 + lane;
-                const bool inb = e < KE && oi[e] != 0xFFFFFFFFu;
-                tk.offer(inb, inb ? ok[e] : -INFINITY, inb ? oi[e] : 0xFFFFFFFFu);
-            }
-        }
-        tk.finish();
-        if (live == 1) {  // the only list of this query: straight to the results
-            for (int e = lane; e < a.k; e += 64) sparse_write(a, b, e, e < KE ? bk[e] : -INFINITY, e < KE ? bi[e] : 0xFFFFFFFFu);
-        } else {
-            const size_t base = ((size_t)b * n_seg + s) * KE;
-            for (int e = lane; e < KE; e += 64) {
-                a.lk[base + e] = bk[e];
-                a.li[base + e] = bi[e];
-            }
-        }
-    }
-    if (live == 1) return;
-    __syncthreads();  // wave 0's list stores are issued; the LDS buffers are free for the merge
-    // the last workgroup of this query merges its `live` lists (release: wave 0's list stores
-    // before the count; acquire: the other lists after it)
-    __shared__ int s_last;
-    if (threadIdx.x == 0) {
-        __threadfence();
-        s_last = atomicAdd(a.done + b, 1) == live - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    const size_t q0 = (size_t)b * n_seg * KE;
-    merge_block<double, uint32_t>(a.lk + q0, a.li + q0, live, KE, KE, KE, a.mk + (size_t)b * KE, a.mi + (size_t)b * KE,
-                                  tkmem);
-    __syncthreads();
-    for (int e = threadIdx.x; e < a.k; e += 256) sparse_write(a, b, e, a.mk[(size_t)b * KE + e], a.mi[(size_t)b * KE + e]);
-    if (threadIdx.x == 0) a.done[b] = 0;  // left zero for the next call on this workspace
+    // fold, per-segment lists, the last workgroup's merge (vdb_sparse_query.h)
+    sparse_finish(a, tk, kbase, ibase, cap, b, s, n_seg, live, tkmem);
 }
 
 size_t sparse_search_lds_bytes(int KE, int n_seg) {

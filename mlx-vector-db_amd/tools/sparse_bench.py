@@ -9,9 +9,18 @@ each the median of repeated calls after warm-up with their range, and for the sp
 bytes the kernel reads per second (every row's offsets and (term, weight) pairs, once per query)
 against the HBM figure DESIGN.md uses.  One JSON line per measurement.
 
+``--inverted`` measures the two kernels behind ``search_sparse`` against each other instead (DESIGN.md
+§21.1): at 10^4, 10^5 and 10^6 rows, both vocabularies, batches of 1 and 64 and queries of 32 and
+1 024 terms, the knob "sparse_inverted" at 2 (the row-major kernel, the baseline) and at 1 (the
+inverted kernel) alternating in one process; every argument in device memory, device events around a
+window of back-to-back calls after warm-up, the median of ``--windows`` windows with their range; the
+two results must be equal in every byte.  Beside each, the host-memory call's wall time as above, and
+per column the ``set_sparse`` time without and with the postings build.
+
 Run it under a time limit of its own (``timeout -k 10 600 python tools/sparse_bench.py``).
 
   python tools/sparse_bench.py [--rows 1000000] [--entries 64] [--reps 15] [--out FILE]
+  python tools/sparse_bench.py --inverted [--inverted-rows 10000 100000 1000000] [--windows 7] [--out FILE]
 """
 import argparse
 import json
@@ -60,10 +69,10 @@ def column(rows, entries, n_terms, rng):
     return indptr, terms, weights
 
 
-def queries(B, n_terms, rng):
+def queries(B, n_terms, rng, length=QUERY_TERMS):
     ts, ws = [], []
     for _ in range(B):
-        t = np.unique(np.minimum((n_terms * rng.random(QUERY_TERMS) ** 3).astype(np.int64), n_terms - 1)).astype(np.int32)
+        t = np.unique(np.minimum((n_terms * rng.random(length) ** 3).astype(np.int64), n_terms - 1)).astype(np.int32)
         ts.append(t)
         ws.append((0.1 + rng.random(t.size)).astype(np.float32))
     indptr = np.zeros(B + 1, np.int64)
@@ -71,8 +80,76 @@ def queries(B, n_terms, rng):
     return indptr, np.concatenate(ts), np.concatenate(ws)
 
 
+def inverted(args, emit):
+    import torch
+    from service import _vdb
+    rng = np.random.default_rng(0)
+    for rows in args.inverted_rows:
+        ix = _vdb.NativeIndex(DIM, METRIC)
+        ix.add(rng.standard_normal((rows, DIM)).astype(np.float32))
+        for n_terms in (30522, 250002):
+            indptr, terms, weights = column(rows, args.entries, n_terms, rng)
+            for knob in (2, 0):  # without and with the postings build
+                ix.set_param("sparse_inverted", knob)
+                ts = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    ix.set_sparse(indptr, terms, weights, n_terms)
+                    ts.append(time.perf_counter() - t0)
+                emit({"what": "set_sparse", "postings": ix.stat("sparse_inverted_built"), "n_terms": n_terms, "rows": rows,
+                      "nnz": int(terms.size), "ms": round(1e3 * sorted(ts)[1], 2), "device_bytes": ix.stat("device_bytes")})
+            for length in (32, 1024):
+                for B in (1, 64):
+                    qi, qt, qw = queries(B, n_terms, rng, length)
+                    dqi, dqt, dqw = (torch.from_numpy(x).to("cuda") for x in (qi, qt, qw))
+                    ds = torch.empty((B, K), dtype=torch.float32, device="cuda")
+                    di = torch.empty((B, K), dtype=torch.int64, device="cuda")
+                    dk = torch.empty((B, K), dtype=torch.float64, device="cuda")
+                    st = torch.cuda.current_stream().cuda_stream
+
+                    def call():
+                        ix.search_sparse_device(dqi.data_ptr(), dqt.data_ptr(), dqw.data_ptr(), B, int(qt.size), K,
+                                                ds.data_ptr(), di.data_ptr(), out_keys_ptr=dk.data_ptr(), stream=st)
+
+                    base = None
+                    for knob in (2, 1):
+                        ix.set_param("sparse_inverted", knob)
+                        before = ix.stat("sparse_inverted_queries")
+                        for _ in range(3):
+                            call()
+                        torch.cuda.synchronize()
+                        assert ix.stat("sparse_inverted_queries") - before == (3 * B if knob == 1 else 0), "not the kernel asked for"
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(); call(); e1.record(); torch.cuda.synchronize()
+                        per = max(int(100.0 / max(e0.elapsed_time(e1), 1e-3)), 5)  # calls per window: about 0.1 s
+                        ws = []
+                        for _ in range(args.windows):
+                            e0.record()
+                            for _ in range(per):
+                                call()
+                            e1.record()
+                            torch.cuda.synchronize()
+                            ws.append(e0.elapsed_time(e1) / per)
+                        ws.sort()
+                        host = _timed(lambda: ix.search_sparse(qi, qt, qw, K), 5, warm=1)
+                        rec = {"what": "search_sparse", "kernel": "rows" if knob == 2 else "inverted", "rows": rows,
+                               "n_terms": n_terms, "query_terms": length, "B": B, "k": K, "mem": "device",
+                               "median_ms": round(ws[len(ws) // 2], 4), "min_ms": round(ws[0], 4), "max_ms": round(ws[-1], 4),
+                               "windows": len(ws), "calls_per_window": per, "host_call_median_ms": host["median_ms"]}
+                        got = tuple(x.cpu().numpy().copy() for x in (ds, di, dk))
+                        if knob == 2:
+                            base = got
+                        else:
+                            rec["equal_to_rows"] = all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(got, base))
+                        emit(rec)
+        ix.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--inverted", action="store_true", help="the two kernels against each other (DESIGN.md §21.1)")
+    ap.add_argument("--inverted-rows", type=int, nargs="+", default=[10_000, 100_000, 1_000_000])
+    ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--entries", type=int, default=64)
     ap.add_argument("--reps", type=int, default=15)
@@ -87,6 +164,12 @@ def main():
         print(line, flush=True)
         lines.append(line)
 
+    if args.inverted:
+        inverted(args, emit)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     V = rng.standard_normal((args.rows, DIM)).astype(np.float32)
     ix = _vdb.NativeIndex(DIM, METRIC)
     ix.add(V)
