@@ -149,7 +149,9 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * chunk of vdb_index_remove's scratch / vdb_index_update's staging, 0 = by bytes), "subset_wgs"
  * (workgroups per query of vdb_index_search_rows, 0 = auto; its stats "subset_searches",
  * "subset_queries", "subset_rows", "subset_bad_ids" are described there; vdb_index_search_range's
- * are "range_searches", "range_queries"), "group_fetch" (rows vdb_index_search_groups' inner
+ * are "range_searches", "range_queries"; "range_mfma" picks the kernel of its scan: 0 = auto, 1 =
+ * the fp32-MFMA one for every call, 2 = never, with the stats "range_mfma_searches",
+ * "range_mfma_queries", "range_mfma_exact_pairs" described there), "group_fetch" (rows vdb_index_search_groups' inner
  * search fetches, 0 = auto, 1..200) and "group_force_exact" (0/1; its stats "group_rows",
  * "group_sets", "group_searches", "group_queries", "group_fallback_queries" are described
  * there; vdb_index_search_mmr's are "mmr_searches", "mmr_queries"; vdb_index_search_recommend's
@@ -338,7 +340,17 @@ int32_t vdb_index_search_rows(vdb_index* idx, const float* queries, int32_t n_qu
  * take a per-search workspace, its stream and one pinned staging copy each way, as
  * vdb_index_search_rows does.  Takes the index's shared lock (add / remove / update / clear wait
  * for queued calls).  An empty index gives counts 0 and every slot "no result".  Stats
- * (cumulative, successful calls): "range_searches", "range_queries". */
+ * (cumulative, successful calls): "range_searches", "range_queries".
+ * Two kernels serve the scan of this call with the same result in every byte.  The first forms the
+ * canonical fp64 key of every (row, query) pair.  The second multiplies rows and queries on the fp32
+ * matrix unit, up to 64 queries per block at every dim, and decides a pair from that product only
+ * where a proven margin puts the canonical key on the same side of the bound; every
+ * other pair, and every product that is NaN or infinite, gets its canonical key as in the first.
+ * Knob "range_mfma": 0 = auto (the default: the second kernel for every batch size, as measured), 1 =
+ * the second kernel for every call, 2 = never; another value -> VDB_ERR_INVALID.  Stats:
+ * "range_mfma_searches", "range_mfma_queries" (the calls and queries the second kernel served; the
+ * range_* pair counts both) and "range_mfma_exact_pairs" (the pairs it rescored in fp64: counted on
+ * the device and read after the calls queued so far). */
 int32_t vdb_index_search_range(vdb_index* idx, const float* queries, int32_t n_queries,
                                const double* thresholds, const uint32_t* row_mask, int32_t mem,
                                int64_t cap, int64_t* out_counts, int64_t* out_indices,

@@ -26,6 +26,7 @@
 #include "vdb_compact_plan.h"
 #include "vdb_subset_plan.h"
 #include "vdb_range_plan.h"
+#include "vdb_range_mfma_plan.h"
 #include "vdb_group_plan.h"
 #include "vdb_filter_plan.h"
 #include "vdb_mmr_plan.h"
@@ -72,6 +73,7 @@ constexpr int kFusedBadWord = 14;         // d_xmax word counting the sets a fus
 constexpr int kMaxsimBadWord = 24;        // d_xmax word counting the sets a MaxSim search found bad on the device
 constexpr int kMaxsimSkippedWord = 25;    // d_xmax word counting the rows MaxSim searches skipped for an id past the slots
 constexpr int kSparseBadWord = 26;        // d_xmax word counting the queries a sparse search found bad on the device
+constexpr int kRangeMfmaExactWord = 28;   // d_xmax word counting the pairs the MFMA range scan rescored in fp64
 constexpr int kSparseFlagWord = 27;       // d_xmax word a device-memory vdb_index_set_sparse's validation writes its causes to
 constexpr size_t kXmaxBytes = 256;        // d_xmax in all (layout: vdb_index_create)
 
@@ -259,6 +261,8 @@ struct vdb_index {
     std::atomic<int64_t> n_subset_searches{0}, n_subset_queries{0}, n_subset_rows{0};
     int64_t subset_wgs = 0;  // knob: workgroups per query of a row-list search (0 = auto)
     std::atomic<int64_t> n_range_searches{0}, n_range_queries{0};  // vdb_index_search_range (successful calls)
+    int64_t range_mfma = 0;  // knob: the fp32-MFMA form of its scan (0 = by the batch size, 1 = every call, 2 = never)
+    std::atomic<int64_t> n_range_mfma_searches{0}, n_range_mfma_queries{0};  // of which: by that form
     // vdb_index_set_groups: the group column [group_n] (a device copy owned by the index), the bitmap
     // of its rows with an id >= 0 (ceil(group_n / 32) words) and whether any id is negative; add,
     // remove and clear drop it (group_set = false), update keeps it
@@ -945,7 +949,8 @@ int32_t vdb_index_create(int32_t dim, int32_t metric, int32_t device, vdb_index*
     // [192, 200) the sets MaxSim searches found bad and [200, 208) the rows they skipped
     // (kMaxsimBadWord, kMaxsimSkippedWord; likewise), [208, 216) the queries sparse searches found
     // bad (kSparseBadWord; likewise), [216, 224) the causes of a device-memory vdb_index_set_sparse
-    // (kSparseFlagWord; zeroed by each such call)
+    // (kSparseFlagWord; zeroed by each such call), [224, 232) the pairs the MFMA range scan rescored
+    // with the canonical key (kRangeMfmaExactWord; cumulative, a clear keeps it)
     if (e == hipSuccess) e = hipMalloc(&ix->d_xmax, kXmaxBytes);
     if (e == hipSuccess) e = zero_now(ix->d_xmax, kXmaxBytes, ix->stream);
     if (e == hipSuccess) e = hipMalloc(&ix->d_i8, 64);
@@ -1156,6 +1161,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "hamming_wgs must be in [0, %d] (0 = auto)", kHamMaxSeg);
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->hamming_wgs = value;
+    } else if (n == "range_mfma") {
+        if (!range_mfma_knob_ok(value))
+            return set_error(VDB_ERR_INVALID, "range_mfma must be 0 (auto), 1 (every call) or 2 (never)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->range_mfma = value;
     } else if (n == "hamming_mfma") {
         if (value < 0 || value > 2)
             return set_error(VDB_ERR_INVALID, "hamming_mfma must be 0 (auto), 1 (whenever eligible) or 2 (never)");
@@ -1277,6 +1287,16 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "subset_rows") *value = ix->n_subset_rows.load();
     else if (n == "range_searches") *value = ix->n_range_searches.load();
     else if (n == "range_queries") *value = ix->n_range_queries.load();
+    else if (n == "range_mfma_searches") *value = ix->n_range_mfma_searches.load();
+    else if (n == "range_mfma_queries") *value = ix->n_range_mfma_queries.load();
+    else if (n == "range_mfma_exact_pairs") {  // counted by the scan kernel: after the searches queued so far
+        HIP_TRY(hipSetDevice(ix->device));
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+        unsigned long long c = 0;
+        HIP_TRY(hipMemcpy(&c, ix->d_xmax + kRangeMfmaExactWord, sizeof(c), hipMemcpyDeviceToHost));
+        *value = (int64_t)c;
+    }
     else if (n == "column_slots") *value = ix->col_mask;
     else if (n == "column_sets") *value = ix->n_column_sets.load();
     else if (n == "filter_calls") *value = ix->n_filter_calls.load();
@@ -2639,7 +2659,10 @@ int32_t vdb_index_search_range(vdb_index* ix, const float* queries, int32_t B, c
     const hipStream_t st = lease.st;
 
     const bool masked = row_mask != nullptr && N > 0;
-    const RangeScratch sc = range_scratch(B, D, ix->Dp, N, cap, host, masked, out_keys != nullptr);
+    // which scan serves the call (vdb_range_mfma_plan.h): the scratch holds that form's query block
+    const bool mfma = range_use_mfma(ix->range_mfma, B, D);
+    const RangeScratch sc = mfma ? range_mfma_scratch(B, D, N, cap, host, masked, out_keys != nullptr)
+                                 : range_scratch(B, D, ix->Dp, N, cap, host, masked, out_keys != nullptr);
     int rc = ws_reserve(w, (size_t)sc.total, st);
     if (rc) return rc;
     char* dev = w->dev;
@@ -2687,8 +2710,13 @@ int32_t vdb_index_search_range(vdb_index* ix, const float* queries, int32_t B, c
         a.cap = cap;
         a.index_offset = index_offset;
         // block after block on this stream over the same scratch
-        for (int b0 = 0; b0 < B; b0 += sc.block)
-            HIP_TRY(launch_range_block(ix->metric, a, b0, std::min(sc.block, B - b0), st));
+        for (int b0 = 0; b0 < B; b0 += sc.block) {
+            const int qb = std::min(sc.block, B - b0);
+            if (mfma)
+                HIP_TRY(launch_range_mfma_block(ix->metric, a, b0, qb, ix->d_xmax + kRangeMfmaExactWord, st));
+            else
+                HIP_TRY(launch_range_block(ix->metric, a, b0, qb, st));
+        }
     }
     if (host) {
         const char* r = nullptr;
@@ -2703,6 +2731,10 @@ int32_t vdb_index_search_range(vdb_index* ix, const float* queries, int32_t B, c
     }
     ix->n_range_searches++;
     ix->n_range_queries += B;
+    if (mfma) {
+        ix->n_range_mfma_searches++;
+        ix->n_range_mfma_queries += B;
+    }
     return VDB_OK;
 }
 

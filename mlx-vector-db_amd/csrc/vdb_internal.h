@@ -345,6 +345,13 @@ struct RangeArgs {
     int64_t cap; int64_t* out_c; int64_t* out_i; float* out_s; double* out_k; int64_t index_offset;
 };
 hipError_t launch_range_block(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st);
+// The launches behind the scan alone (prefix, emit, score), for a scan that has filled H and part.
+hipError_t launch_range_finish(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st);
+// The same block with the fp32-MFMA form of the scan (vdb_range_mfma.hip; vdb_range_mfma_plan.h): the
+// same H and part in every bit, the pairs its margin cannot decide rescored with the canonical key
+// and counted into *exact_pairs (device).  D at most kRangeMfmaMaxDim.
+hipError_t launch_range_mfma_block(int metric, const RangeArgs& a, int b0, int qb, unsigned long long* exact_pairs,
+                                   hipStream_t st);
 
 // Predicate masks (vdb_filter.hip, vdb_index_filter_mask): n_preds predicates (at most 256), predicate
 // p the AND of clauses [offsets[p], offsets[p + 1]) (at most 8 each, n_clauses in all; device copies

@@ -220,6 +220,13 @@ hipError_t launch_range_block(int metric, const RangeArgs& a, int b0, int qb, hi
     VDB_RANGE_SCAN(1, 4) VDB_RANGE_SCAN(1, 8) VDB_RANGE_SCAN(1, 0)
 #undef VDB_RANGE_SCAN
     if (!launched) return hipErrorInvalidValue;
+    return launch_range_finish(metric, a, b0, qb, st);
+}
+
+// prefix, emit and score behind a scan (this file's or vdb_range_mfma.hip's) that has written H and part.
+hipError_t launch_range_finish(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st) {
+    const int64_t n_words = range_n_words(a.N);
+    const int64_t n_chunks = range_n_chunks(n_words);
     hipLaunchKernelGGL(range_prefix_kernel, dim3(qb), dim3(256), 0, st, a.part, n_chunks, a.cnt, a.out_c, b0);
     if (a.cap > 0) {
         hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)range_emit_wgs(n_words), qb), dim3(kRangeEmitWords), 0, st,

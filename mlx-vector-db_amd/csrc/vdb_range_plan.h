@@ -89,11 +89,12 @@ struct RangeScratch {
     int64_t in0, q, thr, mask, in_bytes, out0, out_c, out_i, out_s, out_k, out_bytes;
     int64_t total;
 };
-inline RangeScratch range_scratch(int n_queries, int dim, int Dp, int64_t N, int64_t cap, bool host, bool has_mask,
-                                  bool keys) {
+// (block: the queries per block of the scan that will run, at least 1)
+inline RangeScratch range_scratch_block(int n_queries, int dim, int block, int64_t N, int64_t cap, bool host,
+                                        bool has_mask, bool keys) {
     RangeScratch s{};
     const int64_t B = n_queries;
-    s.block = range_query_block(Dp);
+    s.block = block;
     if (s.block > n_queries) s.block = n_queries > 0 ? n_queries : 1;
     s.n_words = range_n_words(N);
     s.n_chunks = range_n_chunks(s.n_words);
@@ -124,6 +125,10 @@ inline RangeScratch range_scratch(int n_queries, int dim, int Dp, int64_t N, int
     s.out_bytes = o - s.out0;
     s.total = o;
     return s;
+}
+inline RangeScratch range_scratch(int n_queries, int dim, int Dp, int64_t N, int64_t cap, bool host, bool has_mask,
+                                  bool keys) {
+    return range_scratch_block(n_queries, dim, range_query_block(Dp), N, cap, host, has_mask, keys);
 }
 
 // ---- validation of a host-memory call -----------------------------------------------------------

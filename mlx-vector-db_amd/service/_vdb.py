@@ -336,6 +336,8 @@ class NativeIndex:
         _check(self._lib.vdb_index_reserve(self._h, int(rows)))
 
     def set_param(self, name: str, value: int) -> None:
+        """include/vdb.h vdb_index_set_param; e.g. "range_mfma": which kernel scans for search_range
+        (0 = auto, 1 = the fp32-MFMA one for every call, 2 = never; the same result in every byte)."""
         _check(self._lib.vdb_index_set_param(self._h, name.encode(), int(value)))
 
     def set_precision(self, precision: str) -> None:
@@ -349,6 +351,8 @@ class NativeIndex:
         return next(k for k, i in PRECISION_IDS.items() if i == v)
 
     def stat(self, name: str) -> int:
+        """include/vdb.h vdb_index_get_stat; e.g. "range_mfma_searches", "range_mfma_queries" and
+        "range_mfma_exact_pairs" of search_range's fp32-MFMA scan."""
         v = ctypes.c_int64(0)
         _check(self._lib.vdb_index_get_stat(self._h, name.encode(), ctypes.byref(v)))
         return int(v.value)
