@@ -169,7 +169,10 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * vdb_index_search_hamming, 0 = auto, 1..512; the code column's and its stats "code_rows",
  * "code_bytes", "code_sets", "hamming_searches", "hamming_queries" are described there) and
  * "hamming_mfma" (which kernel that call takes: 0 = auto, 1 = the MFMA one whenever eligible, 2 =
- * never; its stats "hamming_mfma_searches", "hamming_mfma_queries" are described there).  The numeric columns and predicate masks have no
+ * never; its stats "hamming_mfma_searches", "hamming_mfma_queries" are described there) and
+ * "hamming_range_mfma" (which scan vdb_index_search_hamming_range takes: 0 = auto, 1 = the MFMA one for
+ * every call, 2 = never; its stats "hamming_range_searches", "hamming_range_queries",
+ * "hamming_range_mfma_searches", "hamming_range_mfma_queries" are described there).  The numeric columns and predicate masks have no
  * knob; their stats "column_slots", "column_sets", "filter_calls", "filter_preds" are described at
  * vdb_index_filter_mask.  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
@@ -795,6 +798,47 @@ int32_t vdb_index_search_hamming(vdb_index* idx, const uint8_t* queries, int32_t
                                  const uint32_t* row_mask, int32_t mem,
                                  int32_t* out_distances, int64_t* out_indices,
                                  int64_t index_offset, void* stream);
+
+/* vdb_index_search_hamming_range: every row within a Hamming radius of each query code, with exact
+ * counts -- "is anything within 6 bits of this hash", "every near-copy of this signature", "how many
+ * near-copies of each new row does the corpus hold" (FAISS' IndexBinaryFlat.range_search).  Top-k
+ * cannot answer these: it returns too few rows when more than k qualify, stops at 1 024 and cannot
+ * count.  It is the contract of vdb_index_search_range carried over to the code column.
+ *   queries      [n_queries, n_bytes] uint8, of the attached width; 0 <= n_queries <= 65 535
+ *   radii        [n_queries] int32, one radius per query
+ *   cap          slots per query, >= 0, n_queries * cap <= 2^36; 0 = count only (out_indices and
+ *                out_distances may then be NULL)
+ *   out_counts   [n_queries] int64, required; out_indices [n_queries, cap] int64;
+ *                out_distances [n_queries, cap] int32
+ *   row_mask, mem, index_offset, stream: as vdb_index_search_hamming; all pointers of one memory kind.
+ * Contract: row r passes query b when its mask bit is set, r < count and popcount(queries[b] XOR
+ * codes[r]) <= radii[b]; equality passes, and a radius of 8 * n_bytes or more passes every eligible
+ * row.  out_counts[b] is the exact number of passing rows, also when it exceeds cap.  The first
+ * min(count, cap) passing rows are written in ascending row id, out_indices = row + index_offset and
+ * out_distances = d; later slots up to cap hold -1 / -1; nothing at or past cap is written.
+ * Distances are integers, so the result is exact as it stands and the same bytes for every metric,
+ * precision setting and memory kind: the fp32 rows and the candidate copies are not read.  Errors,
+ * before anything is launched, both memory kinds, all VDB_ERR_INVALID: no column attached, n_queries
+ * out of range, a bad cap, a NULL queries / radii / out_counts with n_queries > 0, NULL list pointers
+ * with cap > 0, a bad mem; host-memory calls also reject a negative radius (no stat moves).
+ * Device-memory calls read nothing back and are stream-ordered; a negative radius there gives that
+ * query a count of 0 and -1 in all its slots.  n_queries == 0 is VDB_OK; an empty index with an
+ * empty column attached gives counts of 0.  Takes the shared lock and a per-search workspace, with
+ * one pinned staging copy each way for host calls, as vdb_index_search_hamming does.
+ * Two scans turn distances into the hit bitmap the dense range search's prefix and emit kernels
+ * finish, with the same result in every byte: XOR + popcount with one ballot per (tile, query), in
+ * blocks of up to 16 queries, and the int8 matrix instruction in blocks of 64, where a lane packs
+ * its 16 compares and one exchange with lane ^ 32 completes a bitmap word.  Knob
+ * "hamming_range_mfma": 0 = auto (the default: calls of at least 64 queries take the second), 1 =
+ * the second for every call, 2 = never; any other value is VDB_ERR_INVALID.  "hamming_wgs" has no
+ * meaning here: the grid is one workgroup per 512 rows.  Stats: "hamming_range_searches",
+ * "hamming_range_queries" (cumulative over successful calls), "hamming_range_mfma_searches",
+ * "hamming_range_mfma_queries" (those the second scan served); "hamming_searches",
+ * "hamming_queries", "searches", "queries" and every "searches_*" stat stay still. */
+int32_t vdb_index_search_hamming_range(vdb_index* idx, const uint8_t* queries, int32_t n_queries,
+                                       const int32_t* radii, const uint32_t* row_mask, int32_t mem,
+                                       int64_t cap, int64_t* out_counts, int64_t* out_indices,
+                                       int32_t* out_distances, int64_t index_offset, void* stream);
 
 /* --- filter operators: numeric columns and predicate masks on the device -------------
  * Replaces: nothing the reference has.  Its filter is `meta.get(key) == value` alone

@@ -134,6 +134,21 @@ class VectorBinaryQuery(BaseModel):
     oversample: int = Field(default=4, description="Rows fetched per row returned when rescoring")
 
 
+class VectorBinaryRangeQuery(BaseModel):
+    """Every row whose binary code (stored in the row's metadata under ``binary_key``, as hex) is
+    within ``radius`` bits of ``code`` (single) or of each of ``codes`` (batch), nearest first, at most
+    ``limit`` per query; the exact number of matches comes with them.  The store checks the rest (one
+    code width, a radius >= 0); a value outside that is a 400."""
+    user_id: str
+    model_id: str
+    code: Optional[str] = Field(default=None, description="The query's code, hex")
+    codes: Optional[List[str]] = Field(default=None, description="A batch of query codes, hex")
+    radius: int = Field(..., description="Largest Hamming distance of a match, in bits")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    binary_key: str = Field(default="code", description="Metadata key holding each row's code")
+    limit: int = Field(default=1000, ge=1, le=100000, description="Most results returned per query (the nearest ones)")
+
+
 class VectorHybridQuery(BaseModel):
     """Dense and sparse retrieval fused by weighted reciprocal rank: the best ``fetch_k`` rows (null:
     min(200, max(k, 4 k))) for ``query`` and the best ``fetch_k`` for ``sparse`` are fused per row,
@@ -296,6 +311,18 @@ class VectorBinaryQueryResponse(BaseModel):
     # "similarity_score"; a batch request answers with "batch_results", one such list per code
     results: List[Dict[str, Any]]
     batch_results: Optional[List[List[Dict[str, Any]]]] = None
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorBinaryRangeQueryResponse(BaseModel):
+    # nearest first: {"metadata", "distance" (Hamming, an integer), "rank"}; total_matches is the exact
+    # number of rows within the radius and may exceed len(results).  A batch request answers with
+    # "batch_results" and "batch_total_matches", one entry per code.
+    results: List[Dict[str, Any]]
+    total_matches: int
+    batch_results: Optional[List[List[Dict[str, Any]]]] = None
+    batch_total_matches: Optional[List[int]] = None
     query_time_ms: float
     total_vectors_searched: int
 
@@ -695,6 +722,41 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in binary query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Binary query failed: {e}")
+
+    @router.post("/binary_range_query", response_model=VectorBinaryRangeQueryResponse)
+    async def binary_range_query_vectors(request: VectorBinaryRangeQuery, api_key: str = Depends(auth)):
+        """Every row within ``radius`` bits, nearest first, at most ``limit`` of them; ``total_matches``
+        is the exact count.  ``code`` for one query, ``codes`` for a batch.  A bad request (neither or
+        both given, bad hex, a width other than the stored one, a negative radius: the store's
+        ValueError) is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if (request.code is None) == (request.codes is None):
+                raise HTTPException(status_code=400, detail="Give either code or codes")
+            codes = [request.code] if request.code is not None else request.codes
+            loop = asyncio.get_running_loop()
+            got = await loop.run_in_executor(
+                mgr._executor, lambda: store.batch_binary_range_query(codes, request.radius,
+                                                                      filter_metadata=request.filter_metadata,
+                                                                      binary_key=request.binary_key, limit=request.limit))
+            shaped = [[{"metadata": m, "distance": d, "rank": i + 1} for i, (m, d) in enumerate(zip(t[2], t[1]))] for t in got]
+            totals = [t[3] for t in got]
+            single = request.code is not None
+            return VectorBinaryRangeQueryResponse(results=shaped[0] if single else [], total_matches=totals[0] if single else 0,
+                                                  batch_results=None if single else shaped,
+                                                  batch_total_matches=None if single else totals,
+                                                  query_time_ms=(time.time() - t0) * 1000,
+                                                  total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Binary range query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Binary range query failed: {e}")
+        except Exception as e:
+            logger.error("Error in binary range query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Binary range query failed: {e}")
 
     @router.post("/hybrid_query", response_model=VectorHybridQueryResponse)
     async def hybrid_query_vectors(request: VectorHybridQuery, api_key: str = Depends(auth)):

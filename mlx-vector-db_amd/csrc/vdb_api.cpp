@@ -35,6 +35,7 @@
 #include "vdb_sparse_plan.h"
 #include "vdb_sparse_inv_plan.h"
 #include "vdb_hamming_plan.h"
+#include "vdb_hamming_range_plan.h"
 #include "vdb_hybsum_plan.h"
 #include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
@@ -321,6 +322,9 @@ struct vdb_index {
     int64_t hamming_mfma = 0;  // knob: the integer-MFMA form of it (0 = by the batch size, 1 = whenever eligible, 2 = never)
     std::atomic<int64_t> n_code_sets{0}, n_hamming_searches{0}, n_hamming_queries{0};
     std::atomic<int64_t> n_hamming_mfma_searches{0}, n_hamming_mfma_queries{0};
+    int64_t hamming_range_mfma = 0;  // knob: the scan of a Hamming range search (0 = by the batch size, 1 = MFMA always, 2 = never)
+    std::atomic<int64_t> n_hamming_range_searches{0}, n_hamming_range_queries{0};
+    std::atomic<int64_t> n_hamming_range_mfma_searches{0}, n_hamming_range_mfma_queries{0};
     std::atomic<int64_t> n_hybrid_searches{0}, n_hybrid_queries{0};
     // vdb_index_search_hybrid_sum: calls and queries (successful calls)
     std::atomic<int64_t> n_hybsum_searches{0}, n_hybsum_queries{0};
@@ -1171,6 +1175,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "hamming_mfma must be 0 (auto), 1 (whenever eligible) or 2 (never)");
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->hamming_mfma = value;
+    } else if (n == "hamming_range_mfma") {
+        if (value < 0 || value > 2)
+            return set_error(VDB_ERR_INVALID, "hamming_range_mfma must be 0 (auto), 1 (every call) or 2 (never)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->hamming_range_mfma = value;
     } else if (n == "hybrid_sum_wgs") {
         if (value < 0 || value > kHybsumMaxSeg)
             return set_error(VDB_ERR_INVALID, "hybrid_sum_wgs must be in [0, %d] (0 = auto)", kHybsumMaxSeg);
@@ -1353,6 +1362,10 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "hamming_queries") *value = ix->n_hamming_queries.load();
     else if (n == "hamming_mfma_searches") *value = ix->n_hamming_mfma_searches.load();
     else if (n == "hamming_mfma_queries") *value = ix->n_hamming_mfma_queries.load();
+    else if (n == "hamming_range_searches") *value = ix->n_hamming_range_searches.load();
+    else if (n == "hamming_range_queries") *value = ix->n_hamming_range_queries.load();
+    else if (n == "hamming_range_mfma_searches") *value = ix->n_hamming_range_mfma_searches.load();
+    else if (n == "hamming_range_mfma_queries") *value = ix->n_hamming_range_mfma_queries.load();
     else if (n == "hybrid_searches") *value = ix->n_hybrid_searches.load();
     else if (n == "hybrid_queries") *value = ix->n_hybrid_queries.load();
     else if (n == "hybrid_sum_searches") *value = ix->n_hybsum_searches.load();
@@ -4137,6 +4150,106 @@ int32_t vdb_index_search_hamming(vdb_index* ix, const uint8_t* queries, int32_t 
     if (mfma) {
         ix->n_hamming_mfma_searches++;
         ix->n_hamming_mfma_queries += B;
+    }
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_hamming_range(vdb_index* ix, const uint8_t* queries, int32_t B, const int32_t* radii,
+                                       const uint32_t* row_mask, int32_t mem, int64_t cap, int64_t* out_counts,
+                                       int64_t* out_indices, int32_t* out_distances, int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // everything checked before any launch (any bytes are a query; a device-memory call's radii are not read)
+    const bool column = ix->code_set && ix->code_n == N;
+    int64_t at = 0;
+    switch (hamming_range_validate(column, B, cap, mem, queries != nullptr, radii != nullptr, out_counts != nullptr,
+                                   out_indices != nullptr, out_distances != nullptr, radii, &at)) {
+        case kHamRangeNoColumn: return set_error(VDB_ERR_INVALID, "no code column is attached (vdb_index_set_codes)");
+        case kHamRangeBadCount: return set_error(VDB_ERR_INVALID, "n_queries must be in [0, %d], got %d", kHamMaxQueries, B);
+        case kHamRangeBadCap:
+            return set_error(VDB_ERR_INVALID, "cap must be >= 0 and n_queries * cap <= %lld, got cap %lld for %d queries",
+                             (long long)kRangeMaxSlots, (long long)cap, B);
+        case kHamRangeBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+        case kHamRangeNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/radius/count pointer");
+        case kHamRangeNullLists:
+            return set_error(VDB_ERR_INVALID, "out_indices and out_distances are required when cap > 0");
+        case kHamRangeNegRadius:
+            return set_error(VDB_ERR_INVALID, "radii[%lld] = %d: a radius must be >= 0", (long long)at, radii[at]);
+        default: break;
+    }
+    if (B == 0) return VDB_OK;
+    const bool host = mem == VDB_MEM_HOST;
+    // as vdb_index_search_hamming: the caller's stream (device memory: NULL = the null stream), or for
+    // a host-memory call without one the stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const int n_bytes = ix->code_bytes;
+    const int W = ham_words(n_bytes);
+    // which scan serves the call (vdb_hamming_range_plan.h): the scratch holds that scan's query block
+    const bool mfma = ham_range_use_mfma(ix->hamming_range_mfma, B);
+    const int block = ham_range_block(mfma, B, W);
+    const HamRangeScratch sc = hamming_range_scratch(B, n_bytes, block, N, cap, host, masked);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    HamRangeArgs a{};
+    a.queries = queries;
+    a.radii = radii;
+    a.mask = masked ? row_mask : nullptr;
+    a.out_c = out_counts;
+    a.out_i = out_indices;
+    a.out_d = out_distances;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * n_bytes);
+            std::memcpy(h + (sc.radii - sc.in0), radii, (size_t)B * 4);
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.n_words * 4);
+        });
+        if (rc) return rc;
+        a.queries = reinterpret_cast<const uint8_t*>(dev + sc.q);
+        a.radii = reinterpret_cast<const int32_t*>(dev + sc.radii);
+        a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.out_c = reinterpret_cast<int64_t*>(dev + sc.out_c);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_d = reinterpret_cast<int32_t*>(dev + sc.out_d);
+    }
+    if (cap == 0) a.out_i = nullptr, a.out_d = nullptr;
+    if (N == 0) {  // an empty index: counts 0 and every slot -1 / -1
+        HIP_TRY(launch_hamming_range_empty(a.out_c, B, a.out_i, a.out_d, cap, st));
+    } else {
+        a.codes = ix->codes;
+        a.N = N;
+        a.n_bytes = n_bytes;
+        a.W = W;
+        a.H = reinterpret_cast<uint32_t*>(dev + sc.H);
+        a.part = reinterpret_cast<uint32_t*>(dev + sc.part);
+        a.cnt = reinterpret_cast<int64_t*>(dev + sc.cnt);
+        a.cap = cap;
+        a.index_offset = index_offset;
+        // block after block on this stream over the same scratch
+        for (int b0 = 0; b0 < B; b0 += block) HIP_TRY(launch_hamming_range_block(a, mfma, block, b0, std::min(block, B - b0), st));
+    }
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_counts, r + (sc.out_c - sc.out0), (size_t)B * 8);
+        if (cap > 0) {
+            std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * cap * 8);
+            std::memcpy(out_distances, r + (sc.out_d - sc.out0), (size_t)B * cap * 4);
+        }
+    }
+    ix->n_hamming_range_searches++;
+    ix->n_hamming_range_queries += B;
+    if (mfma) {
+        ix->n_hamming_range_mfma_searches++;
+        ix->n_hamming_range_mfma_queries += B;
     }
     return VDB_OK;
 }

@@ -347,6 +347,9 @@ struct RangeArgs {
 hipError_t launch_range_block(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st);
 // The launches behind the scan alone (prefix, emit, score), for a scan that has filled H and part.
 hipError_t launch_range_finish(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st);
+// Prefix and emit alone (counts to out_c, ascending ids to out_i), for a scan of another kind of row
+// that writes H and part in this layout: of `a` only N, H, part, cnt, cap, out_c, out_i, index_offset are read.
+hipError_t launch_range_prefix_emit(const RangeArgs& a, int b0, int qb, hipStream_t st);
 // The same block with the fp32-MFMA form of the scan (vdb_range_mfma.hip; vdb_range_mfma_plan.h): the
 // same H and part in every bit, the pairs its margin cannot decide rescored with the canonical key
 // and counted into *exact_pairs (device).  D at most kRangeMfmaMaxDim.
@@ -515,6 +518,25 @@ hipError_t launch_hamming_search(const HammingArgs& a, int qb, int n_seg, hipStr
 // used and stays zero.
 size_t hamming_mfma_lds_bytes(int W);
 hipError_t launch_hamming_mfma(const HammingArgs& a, int n_seg, hipStream_t st);
+// Hamming range search (vdb_hamming_range.hip, vdb_index_search_hamming_range): queries [b0, b0 + qb)
+// of the batch (qb at most `block`, vdb_hamming_range_plan.h ham_range_block) against rows [0, N),
+// N >= 1.  Row r passes query b when popcount(queries[b] XOR row) <= radii[b] and mask (optional, the
+// row_mask layout) has its bit.  out_c[b] = the exact number of passing rows; with cap > 0 the first
+// min(count, cap) of them in ascending row order go to out_i / out_d [b][cap] and the slots after
+// them get -1 / -1; nothing at or past cap is written.  Scan (popcount or MFMA, the same H and part in
+// every byte), the dense range search's prefix and emit, and with cap > 0 the distance fill, over the
+// scratch H [block][n_words], part [block][n_chunks], cnt [block], which the next block of the same
+// stream reuses.
+struct HamRangeArgs {
+    const uint64_t* codes; int64_t N; int n_bytes; int W;
+    const uint8_t* queries; const int32_t* radii; const uint32_t* mask;
+    uint32_t* H; uint32_t* part; int64_t* cnt;
+    int64_t cap; int64_t* out_c; int64_t* out_i; int32_t* out_d; int64_t index_offset;
+};
+hipError_t launch_hamming_range_block(const HamRangeArgs& a, bool mfma, int block, int b0, int qb, hipStream_t st);
+// An empty index: counts 0 and, with cap > 0, -1 / -1 in every slot.
+hipError_t launch_hamming_range_empty(int64_t* out_c, int n_queries, int64_t* out_i, int32_t* out_d, int64_t cap,
+                                      hipStream_t st);
 
 // Weighted-sum hybrid search (vdb_hybsum.hip, vdb_index_search_hybrid_sum).  Query b is the dense
 // vector Q[b] (qn64[b]: its canonical norm) and the sparse entries [q_indptr[b], q_indptr[b + 1]) of

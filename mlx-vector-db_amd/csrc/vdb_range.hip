@@ -225,18 +225,30 @@ hipError_t launch_range_block(int metric, const RangeArgs& a, int b0, int qb, hi
 
 // prefix, emit and score behind a scan (this file's or vdb_range_mfma.hip's) that has written H and part.
 hipError_t launch_range_finish(int metric, const RangeArgs& a, int b0, int qb, hipStream_t st) {
-    const int64_t n_words = range_n_words(a.N);
-    const int64_t n_chunks = range_n_chunks(n_words);
-    hipLaunchKernelGGL(range_prefix_kernel, dim3(qb), dim3(256), 0, st, a.part, n_chunks, a.cnt, a.out_c, b0);
+    const hipError_t e = launch_range_prefix_emit(a, b0, qb, st);
+    if (e != hipSuccess) return e;
     if (a.cap > 0) {
-        hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)range_emit_wgs(n_words), qb), dim3(kRangeEmitWords), 0, st,
-                           a, b0);
         const dim3 sg(range_score_wgs(a.cap), qb);
         if (metric == 0)
             hipLaunchKernelGGL((range_score_kernel<0>), sg, dim3(256), 0, st, a, b0);
         else
             hipLaunchKernelGGL((range_score_kernel<1>), sg, dim3(256), 0, st, a, b0);
     }
+    return hipGetLastError();
+}
+
+// prefix and emit alone, for any scan that has written H and part in this layout (the Hamming range
+// search's, vdb_hamming_range.hip): of `a` they read N, H, part, cnt, cap, out_c, out_i, index_offset.
+hipError_t launch_range_prefix_emit(const RangeArgs& a, int b0, int qb, hipStream_t st) {
+    if (qb <= 0) return hipSuccess;
+    if (b0 < 0 || a.N <= 0 || a.cap < 0 || !a.H || !a.part || !a.cnt || !a.out_c || (a.cap > 0 && !a.out_i))
+        return hipErrorInvalidValue;
+    const int64_t n_words = range_n_words(a.N);
+    const int64_t n_chunks = range_n_chunks(n_words);
+    hipLaunchKernelGGL(range_prefix_kernel, dim3(qb), dim3(256), 0, st, a.part, n_chunks, a.cnt, a.out_c, b0);
+    if (a.cap > 0)
+        hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)range_emit_wgs(n_words), qb), dim3(kRangeEmitWords), 0, st,
+                           a, b0);
     return hipGetLastError();
 }
 

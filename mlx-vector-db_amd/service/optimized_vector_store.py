@@ -1470,6 +1470,74 @@ class MLXVectorStore:
                             scores[b][valid].astype(np.float64).tolist()))
             return out
 
+    def _binary_range(self, codes, radii, filter_metadata, binary_key: str, count_only: bool):
+        """One vdb_index_search_hamming_range call for a list of codes -> (counts, indices, distances),
+        or None when nothing can match (an empty store, a filter nothing passes, no row with a code)."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("binary range query is not supported on a multi-device store")
+        qs = [normalize_code(c, "the query's code") for c in codes]
+        r = np.asarray(radii, dtype=np.int64)
+        r = np.full(len(qs), int(r), dtype=np.int64) if r.ndim == 0 else r.reshape(-1)
+        if r.size != len(qs):
+            raise ValueError(f"{len(qs)} codes but {r.size} radii")
+        if (r < 0).any():
+            raise ValueError("a radius must be >= 0")
+        with _Read(self._rw):
+            if self._vector_count == 0 or not qs:
+                return None
+            mask = self._sparse_mask(filter_metadata)
+            if mask is False:
+                return None
+            with self._code_lock:  # one attached column: attach and search as one step
+                n_bytes = self._attach_codes(binary_key)
+                if n_bytes == 0:
+                    return None
+                for q in qs:
+                    if q.size != n_bytes:
+                        raise ValueError(f"the query's code holds {q.size} bytes, the stored codes {n_bytes}")
+                have = self._code_mask
+                mask = have if mask is None else (np.asarray(mask, np.uint32)[:have.size] & have)
+                return self._index.search_hamming_range(np.stack(qs), r, cap=0 if count_only else None, mask=mask)
+
+    def binary_range_query(self, code, radius: int, filter_metadata: Optional[Dict] = None, binary_key: str = "code",
+                           limit: Optional[int] = None) -> Tuple:
+        """Every row whose binary code (metadata key ``binary_key``, as ``binary_query`` reads it) is
+        within ``radius`` bits of ``code`` -> (indices, distances, metadata, count), nearest first, ties
+        to the lower row id; a row without a code never matches.  ``count`` is the exact number of rows
+        within the radius; ``limit`` keeps the nearest ``limit`` of them.  Exact, on the device, and not
+        capped at 1024 results as ``binary_query`` is (include/vdb.h vdb_index_search_hamming_range).
+        The reference has no such read."""
+        return self.batch_binary_range_query([code], radius, filter_metadata, binary_key, limit)[0]
+
+    def batch_binary_range_query(self, codes, radii, filter_metadata: Optional[Dict] = None, binary_key: str = "code",
+                                 limit: Optional[int] = None) -> List[Tuple]:
+        """``binary_range_query`` for a list of codes from one device call per pass: one tuple per
+        query.  ``radii``: one per query, or a scalar for all."""
+        if limit is not None and int(limit) < 0:
+            raise ValueError(f"limit must be >= 0, got {limit}")
+        codes = list(codes)
+        res = self._binary_range(codes, radii, filter_metadata, binary_key, False)
+        if res is None:
+            return [([], [], [], 0) for _ in codes]
+        counts, idx, dist = res
+        meta = self._metadata
+        out = []
+        for b in range(len(codes)):
+            n = int(min(counts[b], idx.shape[1]))
+            order = np.lexsort((idx[b, :n], dist[b, :n]))  # distance ascending, then row ascending
+            if limit is not None:
+                order = order[:int(limit)]
+            ib = idx[b, :n][order].tolist()
+            out.append((ib, dist[b, :n][order].astype(np.int64).tolist(), [meta[i] if i < len(meta) else {} for i in ib],
+                        int(counts[b])))
+        return out
+
+    def count_binary_within(self, code, radius: int, filter_metadata: Optional[Dict] = None,
+                            binary_key: str = "code") -> int:
+        """How many rows ``binary_range_query`` would match, from a count-only device call."""
+        res = self._binary_range([code], radius, filter_metadata, binary_key, True)
+        return 0 if res is None else int(res[0][0])
+
     # ---- sparse and hybrid query ----------------------------------------------------------
     def _attach_sparse(self, sparse_key: str) -> int:
         """Make the rows' sparse vectors under the metadata key ``sparse_key`` the sparse column
