@@ -172,7 +172,10 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * never; its stats "hamming_mfma_searches", "hamming_mfma_queries" are described there) and
  * "hamming_range_mfma" (which scan vdb_index_search_hamming_range takes: 0 = auto, 1 = the MFMA one for
  * every call, 2 = never; its stats "hamming_range_searches", "hamming_range_queries",
- * "hamming_range_mfma_searches", "hamming_range_mfma_queries" are described there).  The numeric columns and predicate masks have no
+ * "hamming_range_mfma_searches", "hamming_range_mfma_queries" are described there) and "code_dot_mfma"
+ * (which kernel vdb_index_search_code_dot takes: 0 = auto, 1 = the MFMA one whenever eligible, 2 = never;
+ * its stats "code_dot_searches", "code_dot_queries", "code_dot_mfma_searches", "code_dot_mfma_queries"
+ * are described there).  The numeric columns and predicate masks have no
  * knob; their stats "column_slots", "column_sets", "filter_calls", "filter_preds" are described at
  * vdb_index_filter_mask.  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
@@ -798,6 +801,43 @@ int32_t vdb_index_search_hamming(vdb_index* idx, const uint8_t* queries, int32_t
                                  const uint32_t* row_mask, int32_t mem,
                                  int32_t* out_distances, int64_t* out_indices,
                                  int64_t index_offset, void* stream);
+
+/* vdb_index_search_code_dot: asymmetric code search, the k best rows of each int8 query against the
+ * 1-bit codes -- the stored side stays 1 bit per dimension and the query keeps its precision (an int4
+ * or int8 quantised embedding), the usual first stage in front of a dense rescoring.
+ *   queries      [n_queries, 8 * n_bytes] int8, of the attached column's width; 0 <= n_queries <= 65 535.
+ *                Dimension j pairs with code bit j: bit j % 8 of byte j / 8, least-significant first
+ *                (numpy's unpackbits(..., bitorder="little")).  Every int8 value is a query element,
+ *                -128 included: there is no bad query.
+ *   k            1..1024
+ *   out_scores   [n_queries, k] int32; out_indices [n_queries, k] int64
+ *   row_mask, mem, index_offset, stream: as vdb_index_search_hamming; all pointers of one memory kind.
+ * Contract: s(b, r) = sum_j queries[b][j] * bit_j(codes[r]), an exact integer, |s| <= 8 192 * 128 =
+ * 2^20.  Candidates: the rows below count whose mask bit is set.  Ranking by (s desc, row asc); the
+ * first min(k, candidates) slots hold out_scores = s and out_indices = row + index_offset, later slots
+ * score INT32_MIN and index -1 (a score of -1 is a real score).  The +-1 reading of a code, sum_j q_j
+ * (2 b_j - 1) = 2 s - sum_j q_j, differs per query by a positive factor and a constant and so ranks
+ * identically.  The result is the same bytes for every metric, precision setting and memory kind: the
+ * fp32 rows and the candidate copies are not read.  Errors, before anything is launched, both memory
+ * kinds, all VDB_ERR_INVALID: no column attached, k or n_queries out of range, a NULL queries /
+ * out_scores / out_indices with n_queries > 0, a bad mem (no stat moves).  n_queries == 0 is VDB_OK;
+ * an empty index with an empty column attached gives "no result" everywhere.  Device-memory calls are
+ * stream-ordered and read nothing back; host-memory calls take a per-search workspace, its stream and
+ * pinned staging, as vdb_index_search_hamming does.  Takes the shared lock.
+ * Two kernels serve the call, with the same result in every byte: bit planes of
+ * the query against the code words by AND + popcount, with as many planes as the widest value of a
+ * block of queries needs (an int4 batch costs half an int8 one), at every k and batch; and the int8
+ * matrix instruction, stored bits as 0 / 1 against the query as it is, for k <= 64.  Knob
+ * "code_dot_mfma": 0 = auto (the default: eligible calls of at least 16 queries take the second), 1 =
+ * every eligible call takes it, 2 = never; any other value is VDB_ERR_INVALID.  "hamming_wgs" sets the
+ * workgroups per block of queries for this call too.  Stats, cumulative over successful calls:
+ * "code_dot_searches", "code_dot_queries", and "code_dot_mfma_searches", "code_dot_mfma_queries" for
+ * those the second kernel served; "hamming_*", "searches", "queries" and every "searches_*" stat stay
+ * still. */
+int32_t vdb_index_search_code_dot(vdb_index* idx, const int8_t* queries, int32_t n_queries, int32_t k,
+                                  const uint32_t* row_mask, int32_t mem,
+                                  int32_t* out_scores, int64_t* out_indices,
+                                  int64_t index_offset, void* stream);
 
 /* vdb_index_search_hamming_range: every row within a Hamming radius of each query code, with exact
  * counts -- "is anything within 6 bits of this hash", "every near-copy of this signature", "how many

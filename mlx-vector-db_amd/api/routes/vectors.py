@@ -134,6 +134,23 @@ class VectorBinaryQuery(BaseModel):
     oversample: int = Field(default=4, description="Rows fetched per row returned when rescoring")
 
 
+class VectorBinaryDotQuery(BaseModel):
+    """Asymmetric code search: the ``k`` rows whose binary code (stored in the row's metadata under
+    ``binary_key``, as hex) has the largest dot product with ``query`` (single) or with each of
+    ``queries`` (batch): one number per code bit, quantised to int8 by the store's stated rule.  With
+    ``rescore_vector`` (single only) the best min(k * oversample, 1024) rows are re-ranked by their
+    exact dense score.  The store checks the limits; a value outside them is a 400."""
+    user_id: str
+    model_id: str
+    query: Optional[List[float]] = Field(default=None, description="One value per code bit")
+    queries: Optional[List[List[float]]] = Field(default=None, description="A batch of such queries")
+    k: int = Field(default=10, description="Rows returned")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    binary_key: str = Field(default="code", description="Metadata key holding each row's code")
+    rescore_vector: Optional[List[float]] = Field(default=None, description="Dense vector to re-rank the fetched rows by")
+    oversample: int = Field(default=4, description="Rows fetched per row returned when rescoring")
+
+
 class VectorBinaryRangeQuery(BaseModel):
     """Every row whose binary code (stored in the row's metadata under ``binary_key``, as hex) is
     within ``radius`` bits of ``code`` (single) or of each of ``codes`` (batch), nearest first, at most
@@ -309,6 +326,15 @@ class VectorSparseQueryResponse(BaseModel):
 class VectorBinaryQueryResponse(BaseModel):
     # nearest first: {"metadata", "distance" (Hamming, an integer), "rank"}, with rescore_vector also
     # "similarity_score"; a batch request answers with "batch_results", one such list per code
+    results: List[Dict[str, Any]]
+    batch_results: Optional[List[List[Dict[str, Any]]]] = None
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorBinaryDotQueryResponse(BaseModel):
+    # best first: {"metadata", "score" (the integer dot product), "rank"}, with rescore_vector also
+    # "similarity_score"; a batch request answers with "batch_results", one such list per query
     results: List[Dict[str, Any]]
     batch_results: Optional[List[List[Dict[str, Any]]]] = None
     query_time_ms: float
@@ -722,6 +748,53 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in binary query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Binary query failed: {e}")
+
+    @router.post("/binary_dot_query", response_model=VectorBinaryDotQueryResponse)
+    async def binary_dot_query_vectors(request: VectorBinaryDotQuery, api_key: str = Depends(auth)):
+        """The ``k`` rows with the largest dot product of the query with their code bits, best first;
+        ``query`` for one, ``queries`` for a batch.  A bad request (neither or both given, a length
+        other than the stored codes' bits, a non-finite value, k outside its limits: the store's
+        ValueError) is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if (request.query is None) == (request.queries is None):
+                raise HTTPException(status_code=400, detail="Give either query or queries")
+            if request.queries is not None and request.rescore_vector is not None:
+                raise HTTPException(status_code=400, detail="rescore_vector goes with a single query")
+            loop = asyncio.get_running_loop()
+
+            def shape(t):
+                out = [{"metadata": m, "score": sc, "rank": i + 1} for i, (m, sc) in enumerate(zip(t[2], t[1]))]
+                if len(t) > 3:
+                    for r, sc in zip(out, t[3]):
+                        r["similarity_score"] = sc
+                return out
+
+            if request.query is not None:
+                got = await loop.run_in_executor(
+                    mgr._executor, lambda: store.binary_dot_query(request.query, k=request.k,
+                                                                  filter_metadata=request.filter_metadata,
+                                                                  binary_key=request.binary_key,
+                                                                  rescore_vector=request.rescore_vector,
+                                                                  oversample=request.oversample))
+                results, batch = shape(got), None
+            else:
+                got = await loop.run_in_executor(
+                    mgr._executor, lambda: store.batch_binary_dot_query(
+                        request.queries, k=request.k, filter_metadata=request.filter_metadata, binary_key=request.binary_key))
+                results, batch = [], [shape(t) for t in got]
+            return VectorBinaryDotQueryResponse(results=results, batch_results=batch, query_time_ms=(time.time() - t0) * 1000,
+                                                total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Binary dot query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Binary dot query failed: {e}")
+        except Exception as e:
+            logger.error("Error in binary dot query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Binary dot query failed: {e}")
 
     @router.post("/binary_range_query", response_model=VectorBinaryRangeQueryResponse)
     async def binary_range_query_vectors(request: VectorBinaryRangeQuery, api_key: str = Depends(auth)):

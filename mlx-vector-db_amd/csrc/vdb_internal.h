@@ -518,6 +518,24 @@ hipError_t launch_hamming_search(const HammingArgs& a, int qb, int n_seg, hipStr
 // used and stays zero.
 size_t hamming_mfma_lds_bytes(int W);
 hipError_t launch_hamming_mfma(const HammingArgs& a, int n_seg, hipStream_t st);
+// The code-dot search (vdb_index_search_code_dot): int8 queries [n_queries][8 * n_bytes] in device
+// memory against the packed code column, s(b, r) = sum_j q[b][j] * bit_j(code r).  Row r < N is a
+// candidate when mask (optional, the row_mask layout) has its bit; the best k by (s desc, row asc) go
+// to out_s / out_i [b * k + e], score INT32_MIN / index -1 behind them.  Lists, merge and `done` as
+// HammingArgs'.  Two forms (vdb_code_dot_plan.h): bit planes and popcount (vdb_code_dot.hip; grid
+// (n_seg, blocks of qb = cd_block(k, W, n_queries))) and the int8 MFMA (vdb_code_dot_mfma.hip; grid
+// (n_seg, blocks of kHamMfmaQB), k <= kHamMfmaMaxK, a second launch merges, done is not used).
+struct CodeDotArgs {
+    const uint64_t* codes; int64_t N; int n_bytes; int W;
+    const int8_t* queries; int n_queries;
+    const uint32_t* mask; int k; int KE;
+    float* lk; uint32_t* li; float* mk; uint32_t* mi; int* done;
+    int32_t* out_s; int64_t* out_i; int64_t index_offset;
+};
+size_t code_dot_lds_bytes(int qb, int W, int KE, int n_seg);
+hipError_t launch_code_dot(const CodeDotArgs& a, int qb, int n_seg, hipStream_t st);
+size_t code_dot_mfma_lds_bytes(int W);
+hipError_t launch_code_dot_mfma(const CodeDotArgs& a, int n_seg, hipStream_t st);
 // Hamming range search (vdb_hamming_range.hip, vdb_index_search_hamming_range): queries [b0, b0 + qb)
 // of the batch (qb at most `block`, vdb_hamming_range_plan.h ham_range_block) against rows [0, N),
 // N >= 1.  Row r passes query b when popcount(queries[b] XOR row) <= radii[b] and mask (optional, the

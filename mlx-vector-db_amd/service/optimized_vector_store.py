@@ -132,6 +132,24 @@ def normalize_code(value, what: str) -> np.ndarray:
     return code
 
 
+def quantize_dot_query(value, what: str = "the query") -> np.ndarray:
+    """A query of ``binary_dot_query`` -> int8 [n_bits].  An int8 array is taken as it is.  A float (or
+    wider integer) vector is quantised by one rule, in float64: ``scale = 127 / max|v|``, ``q = rint(v *
+    scale)`` (ties to even); a zero vector gives zeros; a non-finite one raises ValueError."""
+    a = np.asarray(value)
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iuf":
+        raise ValueError(f"{what} must be a non-empty 1-d numeric vector")
+    if a.dtype == np.int8:
+        return np.ascontiguousarray(a)
+    v = a.astype(np.float64)
+    if not np.isfinite(v).all():
+        raise ValueError(f"{what} must be finite")
+    top = float(np.abs(v).max())
+    if top == 0.0:
+        return np.zeros(v.size, dtype=np.int8)
+    return np.rint(v * (127.0 / top)).astype(np.int8)
+
+
 def build_code_column(metadata: List[Dict], n: int, binary_key: str = "code"):
     """The column ``vdb_index_set_codes`` takes, from the first ``n`` rows' metadata -> (codes uint8
     [n, n_bytes], have uint32 row_mask of the rows that carry a code, n_bytes); n_bytes 0: no row has
@@ -1467,6 +1485,74 @@ class MLXVectorStore:
                 ib = ridx[b][valid].tolist()
                 d_of = dict(zip(idx[b].tolist(), dist[b].tolist()))
                 out.append((ib, [int(d_of[i]) for i in ib], [meta[i] if i < len(meta) else {} for i in ib],
+                            scores[b][valid].astype(np.float64).tolist()))
+            return out
+
+    def binary_dot_query(self, query, k: int = 10, filter_metadata: Optional[Dict] = None, binary_key: str = "code",
+                         rescore_vector=None, oversample: int = 4) -> Tuple:
+        """Asymmetric code search: the ``k`` rows whose binary code (metadata key ``binary_key``, as
+        ``binary_query`` reads it) has the largest dot product with ``query``, dimension j against code
+        bit j (bit j % 8 of byte j / 8) -> (indices, scores, metadata), best first, ties to the lower row
+        id; a row without a code is never returned.  ``query``: an int8 array of 8 * n_bytes values,
+        taken as it is, or a float vector of that length, quantised by ``quantize_dot_query``.  Scores
+        are exact integers, on the device (include/vdb.h vdb_index_search_code_dot).  With
+        ``rescore_vector`` the best min(k * oversample, 1024) rows are fetched and the call returns the
+        exact dense top-k of that set -> (indices, scores, metadata, dense scores), best dense score
+        first.  The reference has no such read."""
+        rv = None if rescore_vector is None else [rescore_vector]
+        return self.batch_binary_dot_query([query], k, filter_metadata, binary_key, rv, oversample)[0]
+
+    def batch_binary_dot_query(self, queries, k: int = 10, filter_metadata: Optional[Dict] = None,
+                               binary_key: str = "code", rescore_vectors=None, oversample: int = 4) -> List[Tuple]:
+        """``binary_dot_query`` for a list of queries from one device call: one tuple per query."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("binary dot query is not supported on a multi-device store")
+        k, oversample = int(k), int(oversample)
+        if not 1 <= k <= BINARY_MAX_K:
+            raise ValueError(f"k must be in [1, {BINARY_MAX_K}], got {k}")
+        if oversample < 1:
+            raise ValueError(f"oversample must be >= 1, got {oversample}")
+        qs = [quantize_dot_query(q) for q in queries]
+        B = len(qs)
+        R = None
+        if rescore_vectors is not None:
+            R = np.stack([np.asarray(_as_matrix(v), dtype=np.float32).reshape(-1) for v in rescore_vectors]) if B else None
+            if B and R.shape[0] != B:
+                raise ValueError(f"{B} queries need {B} rescore vectors, got {R.shape[0]}")
+        empty = [([], [], [], []) if rescore_vectors is not None else ([], [], []) for _ in range(B)]
+        with _Read(self._rw):
+            if self._vector_count == 0 or B == 0:
+                return empty
+            mask = self._sparse_mask(filter_metadata)
+            if mask is False:
+                return empty
+            fetch = k if R is None else min(k * oversample, BINARY_MAX_K)
+            with self._code_lock:  # one attached column: attach and search as one step
+                n_bytes = self._attach_codes(binary_key)
+                if n_bytes == 0:
+                    return empty
+                for q in qs:
+                    if q.size != 8 * n_bytes:
+                        raise ValueError(f"the query holds {q.size} values, the stored codes {8 * n_bytes} bits")
+                have = self._code_mask
+                mask = have if mask is None else (np.asarray(mask, np.uint32)[:have.size] & have)
+                sc, idx = self._index.search_code_dot(np.stack(qs), fetch, mask=mask)
+            meta = self._metadata
+            out = []
+            if R is None:
+                for b in range(B):
+                    valid = idx[b] >= 0
+                    ib = idx[b][valid].tolist()
+                    out.append((ib, sc[b][valid].astype(np.int64).tolist(), [meta[i] if i < len(meta) else {} for i in ib]))
+                return out
+            # rescoring: the fetched ids, sorted, are each query's row list of the exact subset search
+            lists = [np.sort(idx[b][idx[b] >= 0]) for b in range(B)]
+            scores, ridx = self._index.search_rows(R, k, lists)
+            for b in range(B):
+                valid = ridx[b] >= 0
+                ib = ridx[b][valid].tolist()
+                s_of = dict(zip(idx[b].tolist(), sc[b].tolist()))
+                out.append((ib, [int(s_of[i]) for i in ib], [meta[i] if i < len(meta) else {} for i in ib],
                             scores[b][valid].astype(np.float64).tolist()))
             return out
 
