@@ -175,7 +175,9 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * "hamming_range_mfma_searches", "hamming_range_mfma_queries" are described there) and "code_dot_mfma"
  * (which kernel vdb_index_search_code_dot takes: 0 = auto, 1 = the MFMA one whenever eligible, 2 = never;
  * its stats "code_dot_searches", "code_dot_queries", "code_dot_mfma_searches", "code_dot_mfma_queries"
- * are described there).  The numeric columns and predicate masks have no
+ * are described there) and "jaccard_mfma" (which kernel vdb_index_search_jaccard takes: 0 = auto, 1 =
+ * the MFMA one whenever eligible, 2 = never; its stats "jaccard_searches", "jaccard_queries",
+ * "jaccard_mfma_searches", "jaccard_mfma_queries" are described there).  The numeric columns and predicate masks have no
  * knob; their stats "column_slots", "column_sets", "filter_calls", "filter_preds" are described at
  * vdb_index_filter_mask.  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
@@ -838,6 +840,40 @@ int32_t vdb_index_search_code_dot(vdb_index* idx, const int8_t* queries, int32_t
                                   const uint32_t* row_mask, int32_t mem,
                                   int32_t* out_scores, int64_t* out_indices,
                                   int64_t index_offset, void* stream);
+
+/* vdb_index_search_jaccard: exact Jaccard / Tanimoto top-k over the code column -- chemical fingerprints
+ * (1 024- and 2 048-bit Morgan / ECFP, 166-bit MACCS), set sketches, tag and shingle sets stored as bit
+ * sets (Milvus' BIN_FLAT with the JACCARD / TANIMOTO metric).  It is not a re-ranking of the Hamming
+ * search: the similarity depends on each row's own popcount.
+ *   queries      [n_queries, n_bytes] uint8, of the attached width; 0 <= n_queries <= 65 535.  Any bytes
+ *                are a query.
+ *   k            1..1024
+ *   out_inter, out_union [n_queries, k] int32; out_indices [n_queries, k] int64
+ *   row_mask, mem, index_offset, stream: as vdb_index_search_hamming; all pointers of one memory kind.
+ * Contract: i(b, r) = popcount(q_b AND x_r), u(b, r) = popcount(q_b OR x_r), similarity s = i / u.  u == 0
+ * happens only when query and row are both all-zero and counts as s = 1: identical sets, distance 0
+ * (scipy.spatial.distance.jaccard's convention).  Candidates: the rows below count whose mask bit is
+ * set.  Ranking by (s descending as an exact rational -- 8190/8191 ranks below 8191/8192, which no fp32
+ * key can tell apart --, row ascending); the first min(k, candidates) slots hold out_inter = i,
+ * out_union = u and out_indices = row + index_offset, later slots -1 / -1 / -1.  The result is integers
+ * and the same bytes for every metric, precision setting, memory kind and kernel: the fp32 rows and the
+ * candidate copies are not read.  Errors, before anything is launched, both memory kinds, all
+ * VDB_ERR_INVALID: no column attached, k or n_queries out of range, a NULL queries / out_inter /
+ * out_union / out_indices with n_queries > 0, a bad mem (no stat moves).  n_queries == 0 is VDB_OK; an
+ * empty index with an empty column attached gives "no result" everywhere.  Device-memory calls are
+ * stream-ordered and read nothing back; host-memory calls take a per-search workspace, its stream and
+ * pinned staging, as vdb_index_search_hamming does.  Takes the shared lock.
+ * Two kernels serve the call: AND + popcount with an fp64 quotient as the ranking key,
+ * at every k and batch; and the int8 matrix instruction, bits as 0 / 1 on both sides, with a 32-bit
+ * integer key, for k <= 64.  Knob "jaccard_mfma": 0 = auto (the default), 1 = every eligible call takes
+ * the second, 2 = never; any other value is VDB_ERR_INVALID.  "hamming_wgs" sets the workgroups per
+ * block of queries for this call too.  Stats, cumulative over successful calls: "jaccard_searches",
+ * "jaccard_queries", and "jaccard_mfma_searches", "jaccard_mfma_queries" for those the second kernel
+ * served; "hamming_*", "code_dot_*", "searches", "queries" and every "searches_*" stat stay still. */
+int32_t vdb_index_search_jaccard(vdb_index* idx, const uint8_t* queries, int32_t n_queries, int32_t k,
+                                 const uint32_t* row_mask, int32_t mem,
+                                 int32_t* out_inter, int32_t* out_union, int64_t* out_indices,
+                                 int64_t index_offset, void* stream);
 
 /* vdb_index_search_hamming_range: every row within a Hamming radius of each query code, with exact
  * counts -- "is anything within 6 bits of this hash", "every near-copy of this signature", "how many

@@ -134,6 +134,20 @@ class VectorBinaryQuery(BaseModel):
     oversample: int = Field(default=4, description="Rows fetched per row returned when rescoring")
 
 
+class VectorBinaryJaccardQuery(BaseModel):
+    """The ``k`` rows whose binary code (stored in the row's metadata under ``binary_key``, as hex), taken
+    as a set of bits, has the largest Jaccard / Tanimoto similarity with ``code`` (single) or with each
+    of ``codes`` (batch).  The store checks the limits (k at most 1024, one code width); a value outside
+    them is a 400."""
+    user_id: str
+    model_id: str
+    code: Optional[str] = Field(default=None, description="The query's code, hex")
+    codes: Optional[List[str]] = Field(default=None, description="A batch of query codes, hex")
+    k: int = Field(default=10, description="Rows returned")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    binary_key: str = Field(default="code", description="Metadata key holding each row's code")
+
+
 class VectorBinaryDotQuery(BaseModel):
     """Asymmetric code search: the ``k`` rows whose binary code (stored in the row's metadata under
     ``binary_key``, as hex) has the largest dot product with ``query`` (single) or with each of
@@ -326,6 +340,16 @@ class VectorSparseQueryResponse(BaseModel):
 class VectorBinaryQueryResponse(BaseModel):
     # nearest first: {"metadata", "distance" (Hamming, an integer), "rank"}, with rescore_vector also
     # "similarity_score"; a batch request answers with "batch_results", one such list per code
+    results: List[Dict[str, Any]]
+    batch_results: Optional[List[List[Dict[str, Any]]]] = None
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorBinaryJaccardQueryResponse(BaseModel):
+    # best first: {"metadata", "similarity" (intersection / union, 1.0 for two empty sets), "distance"
+    # (1 - similarity), "intersection", "union" (the integers), "rank"}; a batch request answers with
+    # "batch_results", one such list per code
     results: List[Dict[str, Any]]
     batch_results: Optional[List[List[Dict[str, Any]]]] = None
     query_time_ms: float
@@ -748,6 +772,45 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in binary query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Binary query failed: {e}")
+
+    @router.post("/binary_jaccard_query", response_model=VectorBinaryJaccardQueryResponse)
+    async def binary_jaccard_query_vectors(request: VectorBinaryJaccardQuery, api_key: str = Depends(auth)):
+        """The ``k`` rows most similar by Jaccard / Tanimoto, best first; ``code`` for one query, ``codes``
+        for a batch.  Status codes as /binary_query: a bad request (neither or both given, bad hex, a
+        width other than the stored one, k outside its limits: the store's ValueError) is a 400, an
+        unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if (request.code is None) == (request.codes is None):
+                raise HTTPException(status_code=400, detail="Give either code or codes")
+            loop = asyncio.get_running_loop()
+
+            def shape(t):
+                return [{"metadata": m, "similarity": s, "distance": 1.0 - s, "intersection": i, "union": u, "rank": r + 1}
+                        for r, (m, s, i, u) in enumerate(zip(t[2], t[1], t[3], t[4]))]
+
+            codes = [request.code] if request.code is not None else request.codes
+            got = await loop.run_in_executor(
+                mgr._executor, lambda: store.batch_binary_jaccard_query(codes, k=request.k,
+                                                                        filter_metadata=request.filter_metadata,
+                                                                        binary_key=request.binary_key, with_counts=True))
+            if request.code is not None:
+                results, batch = shape(got[0]), None
+            else:
+                results, batch = [], [shape(t) for t in got]
+            return VectorBinaryJaccardQueryResponse(results=results, batch_results=batch,
+                                                    query_time_ms=(time.time() - t0) * 1000,
+                                                    total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Binary Jaccard query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Binary Jaccard query failed: {e}")
+        except Exception as e:
+            logger.error("Error in binary Jaccard query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Binary Jaccard query failed: {e}")
 
     @router.post("/binary_dot_query", response_model=VectorBinaryDotQueryResponse)
     async def binary_dot_query_vectors(request: VectorBinaryDotQuery, api_key: str = Depends(auth)):

@@ -37,6 +37,7 @@
 #include "vdb_hamming_plan.h"
 #include "vdb_hamming_range_plan.h"
 #include "vdb_code_dot_plan.h"
+#include "vdb_jaccard_plan.h"
 #include "vdb_hybsum_plan.h"
 #include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
@@ -329,6 +330,9 @@ struct vdb_index {
     int64_t code_dot_mfma = 0;  // knob: the int8-MFMA form of the code-dot search (0 = by the batch size, 1 = whenever eligible, 2 = never)
     std::atomic<int64_t> n_code_dot_searches{0}, n_code_dot_queries{0};
     std::atomic<int64_t> n_code_dot_mfma_searches{0}, n_code_dot_mfma_queries{0};
+    int64_t jaccard_mfma = 0;  // knob: the int8-MFMA form of the Jaccard search (0 = by the batch size, 1 = whenever eligible, 2 = never)
+    std::atomic<int64_t> n_jaccard_searches{0}, n_jaccard_queries{0};
+    std::atomic<int64_t> n_jaccard_mfma_searches{0}, n_jaccard_mfma_queries{0};
     std::atomic<int64_t> n_hybrid_searches{0}, n_hybrid_queries{0};
     // vdb_index_search_hybrid_sum: calls and queries (successful calls)
     std::atomic<int64_t> n_hybsum_searches{0}, n_hybsum_queries{0};
@@ -1189,6 +1193,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "code_dot_mfma must be 0 (auto), 1 (whenever eligible) or 2 (never)");
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->code_dot_mfma = value;
+    } else if (n == "jaccard_mfma") {
+        if (!jaccard_knob_ok(value))
+            return set_error(VDB_ERR_INVALID, "jaccard_mfma must be 0 (auto), 1 (whenever eligible) or 2 (never)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->jaccard_mfma = value;
     } else if (n == "hybrid_sum_wgs") {
         if (value < 0 || value > kHybsumMaxSeg)
             return set_error(VDB_ERR_INVALID, "hybrid_sum_wgs must be in [0, %d] (0 = auto)", kHybsumMaxSeg);
@@ -1379,6 +1388,10 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "code_dot_queries") *value = ix->n_code_dot_queries.load();
     else if (n == "code_dot_mfma_searches") *value = ix->n_code_dot_mfma_searches.load();
     else if (n == "code_dot_mfma_queries") *value = ix->n_code_dot_mfma_queries.load();
+    else if (n == "jaccard_searches") *value = ix->n_jaccard_searches.load();
+    else if (n == "jaccard_queries") *value = ix->n_jaccard_queries.load();
+    else if (n == "jaccard_mfma_searches") *value = ix->n_jaccard_mfma_searches.load();
+    else if (n == "jaccard_mfma_queries") *value = ix->n_jaccard_mfma_queries.load();
     else if (n == "hybrid_searches") *value = ix->n_hybrid_searches.load();
     else if (n == "hybrid_queries") *value = ix->n_hybrid_queries.load();
     else if (n == "hybrid_sum_searches") *value = ix->n_hybsum_searches.load();
@@ -4253,6 +4266,98 @@ int32_t vdb_index_search_code_dot(vdb_index* ix, const int8_t* queries, int32_t 
     if (mfma) {
         ix->n_code_dot_mfma_searches++;
         ix->n_code_dot_mfma_queries += B;
+    }
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_jaccard(vdb_index* ix, const uint8_t* queries, int32_t B, int32_t k, const uint32_t* row_mask,
+                                 int32_t mem, int32_t* out_inter, int32_t* out_union, int64_t* out_indices,
+                                 int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // everything checked before any launch (any bytes are a query: the queries themselves need none)
+    const bool column = ix->code_set && ix->code_n == N;
+    switch (jaccard_validate_call(B, k, queries != nullptr, out_inter != nullptr, out_union != nullptr, out_indices != nullptr,
+                                  mem, column)) {
+        case kJacBadCount: return set_error(VDB_ERR_INVALID, "n_queries must be in [0, %d], got %d", kHamMaxQueries, B);
+        case kJacBadK: return set_error(VDB_ERR_INVALID, "k must be in [1, %d], got %d", kHamMaxK, k);
+        case kJacBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind");
+        case kJacNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/output pointer");
+        case kJacNoColumn: return set_error(VDB_ERR_INVALID, "no code column is attached (vdb_index_set_codes)");
+        default: break;
+    }
+    if (B == 0) return VDB_OK;
+    const bool host = mem == VDB_MEM_HOST;
+    // the stream and the workspace as vdb_index_search_hamming takes them
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const int n_bytes = ix->code_bytes;
+    // the form: the int8 MFMA where the knob or the batch asks for it and k allows, else popcount (vdb_jaccard_plan.h)
+    const bool mfma = jaccard_use_mfma(ix->jaccard_mfma, B, k, n_bytes);
+    const int qb = mfma ? jac_mfma_qb(k) : jac_block(k, B);
+    const int n_blocks = ham_n_blocks(B, qb);
+    const int n_seg = N > 0 ? ham_n_seg(ix->hamming_wgs, N, n_blocks, ix->n_cu) : 1;
+    const JaccardScratch sc = jaccard_scratch(B, n_bytes, k, qb, n_seg, N, host, masked);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    JaccardArgs a{};
+    a.queries = queries;
+    a.mask = masked ? row_mask : nullptr;
+    a.out_n = out_inter;
+    a.out_u = out_union;
+    a.out_i = out_indices;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * n_bytes);
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.mask_words * 4);
+        });
+        if (rc) return rc;
+        a.queries = reinterpret_cast<const uint8_t*>(dev + sc.q);
+        a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.out_n = reinterpret_cast<int32_t*>(dev + sc.out_n);
+        a.out_u = reinterpret_cast<int32_t*>(dev + sc.out_u);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+    }
+    a.codes = ix->codes;
+    a.N = N;
+    a.n_bytes = n_bytes;
+    a.W = ham_words(n_bytes);
+    a.n_queries = B;
+    a.k = k;
+    a.KE = ham_ke(k);
+    a.done = reinterpret_cast<int*>(dev + sc.done);
+    a.lk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.lk) : nullptr;
+    a.li = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.li) : nullptr;
+    a.mk = n_seg > 1 ? reinterpret_cast<double*>(dev + sc.mk) : nullptr;
+    a.mi = n_seg > 1 ? reinterpret_cast<uint32_t*>(dev + sc.mi) : nullptr;
+    a.index_offset = index_offset;
+    // the per-block counters start at zero (the popcount kernel leaves them so; a grown workspace is fresh)
+    if (n_seg > 1 && !mfma) HIP_TRY(hipMemsetAsync(a.done, 0, (size_t)n_blocks * sizeof(int), st));
+    // (an empty index: no row is read, every slot "no result")
+    if (mfma)
+        HIP_TRY(launch_jaccard_mfma(a, n_seg, st));
+    else
+        HIP_TRY(launch_jaccard_search(a, qb, n_seg, st));
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_inter, r + (sc.out_n - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_union, r + (sc.out_u - sc.out0), (size_t)B * k * 4);
+        std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * k * 8);
+    }
+    ix->n_jaccard_searches++;
+    ix->n_jaccard_queries += B;
+    if (mfma) {
+        ix->n_jaccard_mfma_searches++;
+        ix->n_jaccard_mfma_queries += B;
     }
     return VDB_OK;
 }

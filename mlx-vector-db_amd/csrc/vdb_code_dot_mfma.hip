@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(256, 2) code_dot_mfma_kernel(CodeDotArgs a) {
                 }
             }
         }
-        mfma_rank_trip(acc, vm, t, key_hi, nq, k, trip, s_flag, cnt0, cand, thr, cnt);
+        mfma_rank_trip(acc, vm, t, mfma_value_key(key_hi), nq, k, trip, s_flag, cnt0, cand, thr, cnt);
     }
     // what is kept, sorted
     mfma_compact_all(0, nq, k, cand, thr, cnt);

@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) hamming_mfma_kernel(HammingArgs a) {
                 }
             }
         }
-        mfma_rank_trip(acc, vm, t, dist, nq, k, trip, s_flag, cnt0, cand, thr, cnt);
+        mfma_rank_trip(acc, vm, t, mfma_value_key(dist), nq, k, trip, s_flag, cnt0, cand, thr, cnt);
     }
     // what is kept, sorted
     mfma_compact_all(0, nq, k, cand, thr, cnt);

@@ -536,6 +536,25 @@ size_t code_dot_lds_bytes(int qb, int W, int KE, int n_seg);
 hipError_t launch_code_dot(const CodeDotArgs& a, int qb, int n_seg, hipStream_t st);
 size_t code_dot_mfma_lds_bytes(int W);
 hipError_t launch_code_dot_mfma(const CodeDotArgs& a, int n_seg, hipStream_t st);
+// The Jaccard / Tanimoto search (vdb_index_search_jaccard): uint8 queries [n_queries][n_bytes] in device
+// memory against the packed code column, i = popcount(q AND x), u = popcount(q OR x), s = i / u (1 when
+// u == 0).  Row r < N is a candidate when mask (optional, the row_mask layout) has its bit; the best k
+// by (s desc as an exact rational, row asc) go to out_n (i) / out_u (u) / out_i [b * k + e], -1 / -1 /
+// -1 behind them.  Lists, merge and `done` as HammingArgs', with fp64 keys.  Two forms
+// (vdb_jaccard_plan.h): popcount (vdb_jaccard.hip; grid (n_seg, blocks of qb = jac_block(k, n_queries)))
+// and the int8 MFMA (vdb_jaccard_mfma.hip; grid (n_seg, blocks of kHamMfmaQB), k <= kHamMfmaMaxK, a
+// second launch merges, done is not used).
+struct JaccardArgs {
+    const uint64_t* codes; int64_t N; int n_bytes; int W;
+    const uint8_t* queries; int n_queries;
+    const uint32_t* mask; int k; int KE;
+    double* lk; uint32_t* li; double* mk; uint32_t* mi; int* done;
+    int32_t* out_n; int32_t* out_u; int64_t* out_i; int64_t index_offset;
+};
+size_t jaccard_search_lds_bytes(int qb, int W, int KE, int n_seg);
+hipError_t launch_jaccard_search(const JaccardArgs& a, int qb, int n_seg, hipStream_t st);
+size_t jaccard_mfma_lds_bytes(int W);
+hipError_t launch_jaccard_mfma(const JaccardArgs& a, int n_seg, hipStream_t st);
 // Hamming range search (vdb_hamming_range.hip, vdb_index_search_hamming_range): queries [b0, b0 + qb)
 // of the batch (qb at most `block`, vdb_hamming_range_plan.h ham_range_block) against rows [0, N),
 // N >= 1.  Row r passes query b when popcount(queries[b] XOR row) <= radii[b] and mask (optional, the

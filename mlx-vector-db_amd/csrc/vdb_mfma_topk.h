@@ -1,8 +1,14 @@
-// vdb_mfma_topk.h: the top-k of the two integer-MFMA searches over the code column (vdb_hamming_mfma.hip,
-// vdb_code_dot_mfma.hip), on the device.  Both hold, per trip and wave, four 32 x 32 i32 accumulators
+// vdb_mfma_topk.h: the top-k of the integer-MFMA searches over the code column (vdb_hamming_mfma.hip,
+// vdb_code_dot_mfma.hip, vdb_jaccard_mfma.hip), on the device.  Each holds, per trip and wave, four 32 x 32 i32 accumulators
 // (two 32-row sub-tiles of a tile against two tiles of 32 queries) and rank rows by a 64-bit key,
 // smaller is better: key = hi << 32 | row, where hi comes from an accumulator value by the one thing
-// the two differ in, the `key_hi` functor (the distance; the biased negated score).
+// the searches differ in, the `rank` object.  rank.hi(qt, rt, v, value) is the key's upper half of the
+// value in register v of the accumulator of sub-tile rt and query tile qt (the lane's query: 32 qt + lane
+// % 32; the row within the sub-tile: mfma_acc_row(v)); rank.pass(qt, rt, v, value, row, th) says whether
+// that entry's key is below the threshold th, and may do so without forming the key (the Jaccard search,
+// vdb_jaccard_mfma.hip, whose key costs a division and depends on the row's popcount).  The Hamming and
+// the code-dot search need the value alone: MfmaValueKey wraps their `key_hi(qt, value)` functor (the
+// distance; the biased negated score).
 //
 // Each query has, in LDS, its threshold (the k-th best key so far) and one candidate buffer shared by
 // the four waves.  A lane holds one query and 16 rows of an accumulator; it tests a register against
@@ -44,14 +50,28 @@ __device__ __forceinline__ ham_i32x4 expand_row16(uint64_t x, int sh) {
     return r;
 }
 
-// A wave offers its tile's accumulators.  vm[rt]: the candidate rows of sub-tile rt as bits;
-// key_hi(qt, value): the key's upper half of an accumulator value of query tile qt.  Returns the flag
-// bits of the header comment.
+// The accumulator layout: the row, within its sub-tile of 32, of register v of a lane.
+__device__ __forceinline__ int mfma_acc_row(int v) { return 8 * (v >> 2) + 4 * (int)((threadIdx.x & 63) >> 5) + (v & 3); }
+
+// A key that is a function of the accumulator value (and the query tile) alone.
 template <class KeyHi>
-__device__ __forceinline__ int mfma_offer(const ham_i32x16 (&acc)[RT][QT], const uint32_t (&vm)[RT], int64_t t, KeyHi key_hi,
+struct MfmaValueKey {
+    KeyHi key_hi;
+    __device__ __forceinline__ uint32_t hi(int qt, int, int, int value) const { return key_hi(qt, value); }
+    __device__ __forceinline__ bool pass(int qt, int, int, int value, uint32_t row, uint64_t th) const {
+        return (((uint64_t)key_hi(qt, value) << 32) | row) < th;
+    }
+};
+template <class KeyHi>
+__device__ __forceinline__ MfmaValueKey<KeyHi> mfma_value_key(KeyHi key_hi) { return MfmaValueKey<KeyHi>{key_hi}; }
+
+// A wave offers its tile's accumulators.  vm[rt]: the candidate rows of sub-tile rt as bits;
+// rank: the key of an entry (the header comment).  Returns the flag bits of the header comment.
+template <class Rank>
+__device__ __forceinline__ int mfma_offer(const ham_i32x16 (&acc)[RT][QT], const uint32_t (&vm)[RT], int64_t t, const Rank& rank,
                                           int nq, int k_high, uint64_t* cand, const uint64_t* thr, int* cnt) {
     const int lane = threadIdx.x & 63;
-    const int col = lane & 31, half = lane >> 5;
+    const int col = lane & 31;
     int flag = 0;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -63,13 +83,13 @@ __device__ __forceinline__ int mfma_offer(const ham_i32x16 (&acc)[RT][QT], const
             const uint64_t th = q < nq ? thr[q] : 0ull;  // an absent query passes nothing
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int rl = 8 * (v >> 2) + 4 * half + (v & 3);  // the accumulator layout: row of register v
+                const int rl = mfma_acc_row(v);
                 const uint32_t row = (uint32_t)(t * kHamTileRows + 32 * rt + rl);
-                const uint32_t d = key_hi(qt, acc[rt][qt][v]);
-                const uint64_t key = ((uint64_t)d << 32) | row;
-                const bool pass = ((vm[rt] >> rl) & 1u) && key < th;
+                const int value = acc[rt][qt][v];
+                const bool pass = ((vm[rt] >> rl) & 1u) && rank.pass(qt, rt, v, value, row, th);
                 if (__ballot(pass) == 0ull) continue;
                 if (pass) {
+                    const uint64_t key = ((uint64_t)rank.hi(qt, rt, v, value) << 32) | row;
                     const int pos = atomicAdd(&cnt[q], 1);
                     if (pos < CAP) {
                         cand[(size_t)q * CAP + pos] = key;
@@ -135,15 +155,15 @@ __device__ __forceinline__ void mfma_compact_all(int above, int nq, int k, uint6
 // alone.  (The first trip starts at round 1: without thresholds every row passes and round 0 would
 // only find the buffers full.)  s_flag: two words of LDS, zero before the first trip; cnt0: thread q <
 // QB's copy of query q's count at the trip's start, kept up to date here.
-template <class KeyHi>
+template <class Rank>
 __device__ __forceinline__ void mfma_rank_trip(const ham_i32x16 (&acc)[RT][QT], const uint32_t (&vm)[RT], int64_t t,
-                                               KeyHi key_hi, int nq, int k, int trip, int* s_flag, int& cnt0, uint64_t* cand,
+                                               const Rank& rank, int nq, int k, int trip, int* s_flag, int& cnt0, uint64_t* cand,
                                                uint64_t* thr, int* cnt) {
     const int wv = threadIdx.x >> 6;
     const bool has_tile = (vm[0] | vm[1]) != 0u;
     for (int r = trip == 0 ? 1 : 0; r <= kHamWaves; ++r) {
         if (has_tile && (r == 0 || wv == r - 1)) {
-            const int flag = mfma_offer(acc, vm, t, key_hi, nq, kHamMfmaHigh, cand, thr, cnt);
+            const int flag = mfma_offer(acc, vm, t, rank, nq, kHamMfmaHigh, cand, thr, cnt);
             if (r == 0 && flag) atomicOr(&s_flag[trip & 1], flag);
         }
         __syncthreads();  // the round's appends are made

@@ -58,7 +58,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_set_column", "vdb_index_filter_mask",
     "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim",
     "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_index_search_hybrid_sum",
-    "vdb_index_set_codes", "vdb_index_search_hamming", "vdb_index_search_hamming_range", "vdb_index_search_code_dot", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_codes", "vdb_index_search_hamming", "vdb_index_search_hamming_range", "vdb_index_search_code_dot", "vdb_index_search_jaccard", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -147,6 +147,7 @@ def load_library():
             "vdb_index_set_codes": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
             "vdb_index_search_hamming": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
             "vdb_index_search_code_dot": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
+            "vdb_index_search_jaccard": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_index_search_hamming_range": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64,
                                                        c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
@@ -947,6 +948,33 @@ class NativeIndex:
             self._h, ctypes.c_void_p(queries_ptr or None), int(n_queries), int(k), ctypes.c_void_p(mask_ptr or None),
             MEM_DEVICE, ctypes.c_void_p(out_scores_ptr or None), ctypes.c_void_p(out_idx_ptr or None), int(index_offset),
             ctypes.c_void_p(stream or None)))
+
+    def search_jaccard(self, queries, k: int, mask: Optional[np.ndarray] = None, index_offset: int = 0):
+        """include/vdb.h vdb_index_search_jaccard, host memory: ``queries`` uint8 ``[B, n_bytes]`` of the
+        attached width; the rows whose ``mask`` bit is set rank by (|q AND x| / |q OR x| desc as an exact
+        rational, two empty sets counting as 1, row asc).  Returns (intersections i32 [B,k], unions i32
+        [B,k], indices i64 [B,k]); slots past min(k, candidates) are -1 / -1 / -1.  Needs a column
+        (``set_codes``); ``k`` outside [1, 1024] raises ValueError."""
+        q = self._codes(queries, "queries")
+        width = self.stat("code_bytes")
+        if q.shape[0] and width and q.shape[1] != width:
+            raise ValueError(f"queries are {q.shape[1]} bytes wide, the attached codes {width}")
+        B, k = q.shape[0], int(k)
+        inter = np.empty((B, max(k, 0)), dtype=np.int32)  # (a bad k is the library's to refuse)
+        union = np.empty((B, max(k, 0)), dtype=np.int32)
+        idx = np.empty((B, max(k, 0)), dtype=np.int64)
+        m, mask_p = self._mask_ptr(mask)
+        _check(self._lib.vdb_index_search_jaccard(self._h, _ptr(q) if q.size else None, B, k, mask_p, MEM_HOST,
+                                                  _ptr(inter), _ptr(union), _ptr(idx), int(index_offset), None))
+        return inter, union, idx
+
+    def search_jaccard_device(self, queries_ptr: int, n_queries: int, k: int, out_inter_ptr: int, out_union_ptr: int,
+                              out_idx_ptr: int, mask_ptr: int = 0, index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_jaccard with device-memory arguments; stream-ordered, nothing is read back."""
+        _check(self._lib.vdb_index_search_jaccard(
+            self._h, ctypes.c_void_p(queries_ptr or None), int(n_queries), int(k), ctypes.c_void_p(mask_ptr or None),
+            MEM_DEVICE, ctypes.c_void_p(out_inter_ptr or None), ctypes.c_void_p(out_union_ptr or None),
+            ctypes.c_void_p(out_idx_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
 
     def search_hamming_range(self, queries, radii, cap: Optional[int] = None, mask: Optional[np.ndarray] = None,
                              index_offset: int = 0):

@@ -1556,6 +1556,54 @@ class MLXVectorStore:
                             scores[b][valid].astype(np.float64).tolist()))
             return out
 
+    def binary_jaccard_query(self, code, k: int = 10, filter_metadata: Optional[Dict] = None, binary_key: str = "code",
+                             with_counts: bool = False) -> Tuple:
+        """The ``k`` rows whose binary code (metadata key ``binary_key``, as ``binary_query`` reads it),
+        taken as a set of bits, has the largest Jaccard / Tanimoto similarity |q AND x| / |q OR x| with
+        ``code`` -> (indices, similarities, metadata), best first, ties to the lower row id; a row
+        without a code is never returned.  Two empty sets are identical: similarity 1.0.  The ranking is
+        exact on the ratio itself, on the device (include/vdb.h vdb_index_search_jaccard); the
+        similarity returned is the Python float ``i / u``.  ``with_counts`` appends the integers
+        (intersections, unions) to the tuple.  The reference has no such read."""
+        return self.batch_binary_jaccard_query([code], k, filter_metadata, binary_key, with_counts)[0]
+
+    def batch_binary_jaccard_query(self, codes, k: int = 10, filter_metadata: Optional[Dict] = None,
+                                   binary_key: str = "code", with_counts: bool = False) -> List[Tuple]:
+        """``binary_jaccard_query`` for a list of codes from one device call: one tuple per query."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("binary Jaccard query is not supported on a multi-device store")
+        k = int(k)
+        if not 1 <= k <= BINARY_MAX_K:
+            raise ValueError(f"k must be in [1, {BINARY_MAX_K}], got {k}")
+        qs = [normalize_code(c, "the query's code") for c in codes]
+        B = len(qs)
+        empty = [([], [], [], [], []) if with_counts else ([], [], []) for _ in range(B)]
+        with _Read(self._rw):
+            if self._vector_count == 0 or B == 0:
+                return empty
+            mask = self._sparse_mask(filter_metadata)
+            if mask is False:
+                return empty
+            with self._code_lock:  # one attached column: attach and search as one step
+                n_bytes = self._attach_codes(binary_key)
+                if n_bytes == 0:
+                    return empty
+                for q in qs:
+                    if q.size != n_bytes:
+                        raise ValueError(f"the query's code holds {q.size} bytes, the stored codes {n_bytes}")
+                have = self._code_mask
+                mask = have if mask is None else (np.asarray(mask, np.uint32)[:have.size] & have)
+                inter, union, idx = self._index.search_jaccard(np.stack(qs), k, mask=mask)
+            meta = self._metadata
+            out = []
+            for b in range(B):
+                valid = idx[b] >= 0
+                ib = idx[b][valid].tolist()
+                ii, uu = inter[b][valid].tolist(), union[b][valid].tolist()
+                hit = (ib, [i / u if u else 1.0 for i, u in zip(ii, uu)], [meta[i] if i < len(meta) else {} for i in ib])
+                out.append(hit + (ii, uu) if with_counts else hit)
+            return out
+
     def _binary_range(self, codes, radii, filter_metadata, binary_key: str, count_only: bool):
         """One vdb_index_search_hamming_range call for a list of codes -> (counts, indices, distances),
         or None when nothing can match (an empty store, a filter nothing passes, no row with a code)."""
