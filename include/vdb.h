@@ -916,6 +916,49 @@ int32_t vdb_index_search_hamming_range(vdb_index* idx, const uint8_t* queries, i
                                        int64_t cap, int64_t* out_counts, int64_t* out_indices,
                                        int32_t* out_distances, int64_t index_offset, void* stream);
 
+/* Encoding on the device: the code column derived from the stored rows, and query vectors encoded by
+ * the same rule -- binary quantisation of the dense embeddings (Qdrant / Weaviate BQ, Elasticsearch
+ * BBQ, SimHash), in front of the Hamming searches above and a dense rescoring.
+ *   proj        [n_bits, dim] fp32 row-major, 1 <= n_bits <= 8 192; NULL = the identity projection,
+ *               which needs n_bits == dim (plain sign-bit quantisation)
+ *   thresholds  [n_bits] fp64, NULL = zeros (fp64 so that a caller's P mu for mean-centring is not
+ *               lost to fp32)
+ * The bit rule: bit j of vector x is 1 iff s_j > t_j, where s_j is the canonical fp64 dot product of
+ * proj[j] and x (the sum the cosine key accumulates before its division: separate multiply and add in
+ * the canonical order, then the butterfly; csrc/vdb_common.h); under the identity projection s_j =
+ * (double)x[j].  A plain fp64 `>`: a NaN on either side gives 0, s_j == t_j gives 0.  There is no bad
+ * datum: NaN and infinity have defined bits.  Bit j is bit j % 8 of byte j / 8 (least significant
+ * first, the convention of the code-dot search); n_bytes = ceil(n_bits / 8), pad bits 0.
+ *
+ * The first call encodes rows [0, count) -- the raw stored rows, as vdb_index_get_vectors returns
+ * them, under both metrics: cosine rows are not normalised first (with zero thresholds the sign does
+ * not depend on scale; with thresholds the caller centres in raw space) -- and attaches the result
+ * exactly as vdb_index_set_codes would attach the same bytes: the same tiled layout, lifetime,
+ * "code_rows" / "code_bytes" / "code_sets" stats and locking (exclusive; queued searches are waited
+ * for; returns when done).  proj and thresholds are of memory kind `mem`; device memory is read after
+ * the work queued on `stream`.  vdb_index_update keeps the column as it keeps any other, so the
+ * updated rows' codes are stale until the caller encodes again.
+ *
+ * The second call applies the same rule to vectors [n][dim] and writes out_codes [n][n_bytes]
+ * row-major.  All pointers are of one memory kind.  It takes the shared lock, is stream-ordered and
+ * reads nothing back in device memory; n == 0 is VDB_OK.  The index supplies the dim, the device and
+ * the workspace pool; its rows are not read.
+ *
+ * Errors, before anything is launched, all VDB_ERR_INVALID (no stat moves): n_bits out of range, a
+ * NULL proj with n_bits != dim, a bad mem, a NULL vectors or out_codes with n > 0, n out of [0, 2^31).
+ * Two paths, the same bytes: an fp32 matrix-instruction kernel decides every (vector, bit) pair whose
+ * margin allows it and a second pass decides the rest with the canonical fp64 sum.
+ * Knob "encode_mfma": 0 (default) as described, 2 = every pair in fp64; any other value is
+ * VDB_ERR_INVALID.  The bytes are identical for both knob values, both memory kinds, both metrics and
+ * every precision setting.  Stats, cumulative over successful calls of either kind: "encode_calls",
+ * "encode_vectors", "encode_pairs" (vectors x bits), "encode_exact_pairs" (pairs decided in fp64; the
+ * identity projection needs no sum and counts none). */
+int32_t vdb_index_encode_codes(vdb_index* idx, const float* proj, const double* thresholds,
+                               int32_t n_bits, int32_t mem, void* stream);
+int32_t vdb_index_encode(vdb_index* idx, const float* vectors, int64_t n,
+                         const float* proj, const double* thresholds, int32_t n_bits,
+                         int32_t mem, uint8_t* out_codes, void* stream);
+
 /* --- filter operators: numeric columns and predicate masks on the device -------------
  * Replaces: nothing the reference has.  Its filter is `meta.get(key) == value` alone
  * (service/optimized_vector_store.py:159-165); range filters ("timestamp >= t", "price between a

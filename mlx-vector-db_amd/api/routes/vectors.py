@@ -134,6 +134,26 @@ class VectorBinaryQuery(BaseModel):
     oversample: int = Field(default=4, description="Rows fetched per row returned when rescoring")
 
 
+class VectorQuantizedQuery(BaseModel):
+    """Binary-quantised search of the dense rows: the store derives one code per row on the device,
+    encodes ``query`` (single) or each of ``queries`` (batch) by the same rule, fetches the nearest
+    min(k * oversample, 1024) rows in Hamming distance and, with ``rescore``, re-ranks them by their
+    exact dense score.  The quantizer fields are applied when the store has no quantizer yet.  The
+    store checks the limits; a value outside them is a 400."""
+    user_id: str
+    model_id: str
+    query: Optional[List[float]] = Field(default=None, description="The query vector")
+    queries: Optional[List[List[float]]] = Field(default=None, description="A batch of query vectors")
+    k: int = Field(default=10, description="Rows returned")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    oversample: int = Field(default=4, description="Rows fetched per row returned when rescoring")
+    rescore: bool = Field(default=True, description="Re-rank the fetched rows by their exact dense score")
+    quantizer_kind: str = Field(default="sign", description="'sign' (one bit per dim) or 'simhash' (random projections)")
+    quantizer_bits: Optional[int] = Field(default=None, description="Bits per code ('simhash'; default: the dim)")
+    quantizer_center: bool = Field(default=True, description="Threshold at the mean of the rows present")
+    quantizer_seed: int = Field(default=0, description="Seed of the 'simhash' projection")
+
+
 class VectorBinaryJaccardQuery(BaseModel):
     """The ``k`` rows whose binary code (stored in the row's metadata under ``binary_key``, as hex), taken
     as a set of bits, has the largest Jaccard / Tanimoto similarity with ``code`` (single) or with each
@@ -772,6 +792,50 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in binary query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Binary query failed: {e}")
+
+    @router.post("/quantized_query", response_model=VectorBinaryQueryResponse)
+    async def quantized_query_vectors(request: VectorQuantizedQuery, api_key: str = Depends(auth)):
+        """The ``k`` best rows by binary-quantised search with dense rescoring; ``query`` for one vector,
+        ``queries`` for a batch.  Results as /binary_query's.  Status codes as /binary_query: the store's
+        ValueError is a 400, an unsupported store a 501, anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if (request.query is None) == (request.queries is None):
+                raise HTTPException(status_code=400, detail="Give either query or queries")
+            loop = asyncio.get_running_loop()
+
+            def shape(t):
+                out = [{"metadata": m, "distance": d, "rank": i + 1} for i, (m, d) in enumerate(zip(t[2], t[1]))]
+                if len(t) > 3:
+                    for r, sc in zip(out, t[3]):
+                        r["similarity_score"] = sc
+                return out
+
+            def run():
+                # (a store that has a quantizer keeps it: the request's quantizer fields are then not read)
+                store.ensure_quantizer(request.quantizer_kind, request.quantizer_bits, request.quantizer_center,
+                                       request.quantizer_seed)
+                vs = [request.query] if request.query is not None else request.queries
+                return store.batch_quantized_query(vs, k=request.k, filter_metadata=request.filter_metadata,
+                                                   oversample=request.oversample, rescore=request.rescore)
+
+            got = await loop.run_in_executor(mgr._executor, run)
+            if request.query is not None:
+                results, batch = shape(got[0]), None
+            else:
+                results, batch = [], [shape(t) for t in got]
+            return VectorBinaryQueryResponse(results=results, batch_results=batch, query_time_ms=(time.time() - t0) * 1000,
+                                             total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Quantized query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Quantized query failed: {e}")
+        except Exception as e:
+            logger.error("Error in quantized query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Quantized query failed: {e}")
 
     @router.post("/binary_jaccard_query", response_model=VectorBinaryJaccardQueryResponse)
     async def binary_jaccard_query_vectors(request: VectorBinaryJaccardQuery, api_key: str = Depends(auth)):

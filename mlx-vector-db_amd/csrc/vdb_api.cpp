@@ -38,6 +38,7 @@
 #include "vdb_hamming_range_plan.h"
 #include "vdb_code_dot_plan.h"
 #include "vdb_jaccard_plan.h"
+#include "vdb_encode_plan.h"
 #include "vdb_hybsum_plan.h"
 #include "vdb_recommend_plan.h"
 #include "vdb_search_plan.h"
@@ -77,6 +78,7 @@ constexpr int kMaxsimBadWord = 24;        // d_xmax word counting the sets a Max
 constexpr int kMaxsimSkippedWord = 25;    // d_xmax word counting the rows MaxSim searches skipped for an id past the slots
 constexpr int kSparseBadWord = 26;        // d_xmax word counting the queries a sparse search found bad on the device
 constexpr int kRangeMfmaExactWord = 28;   // d_xmax word counting the pairs the MFMA range scan rescored in fp64
+constexpr int kEncodeExactWord = 29;      // d_xmax word counting the pairs an encode decided in fp64
 constexpr int kSparseFlagWord = 27;       // d_xmax word a device-memory vdb_index_set_sparse's validation writes its causes to
 constexpr size_t kXmaxBytes = 256;        // d_xmax in all (layout: vdb_index_create)
 
@@ -330,6 +332,11 @@ struct vdb_index {
     int64_t code_dot_mfma = 0;  // knob: the int8-MFMA form of the code-dot search (0 = by the batch size, 1 = whenever eligible, 2 = never)
     std::atomic<int64_t> n_code_dot_searches{0}, n_code_dot_queries{0};
     std::atomic<int64_t> n_code_dot_mfma_searches{0}, n_code_dot_mfma_queries{0};
+    // vdb_index_encode_codes / vdb_index_encode: knob (0 = the fp32 MFMA decides what its margin allows, 2 =
+    // every pair in fp64) and successful calls, their vectors and pairs (vectors x bits); the pairs decided
+    // in fp64 are counted on the device (d_xmax + kEncodeExactWord)
+    int64_t encode_mfma = 0;
+    std::atomic<int64_t> n_encode_calls{0}, n_encode_vectors{0}, n_encode_pairs{0};
     int64_t jaccard_mfma = 0;  // knob: the int8-MFMA form of the Jaccard search (0 = by the batch size, 1 = whenever eligible, 2 = never)
     std::atomic<int64_t> n_jaccard_searches{0}, n_jaccard_queries{0};
     std::atomic<int64_t> n_jaccard_mfma_searches{0}, n_jaccard_mfma_queries{0};
@@ -962,7 +969,8 @@ int32_t vdb_index_create(int32_t dim, int32_t metric, int32_t device, vdb_index*
     // (kMaxsimBadWord, kMaxsimSkippedWord; likewise), [208, 216) the queries sparse searches found
     // bad (kSparseBadWord; likewise), [216, 224) the causes of a device-memory vdb_index_set_sparse
     // (kSparseFlagWord; zeroed by each such call), [224, 232) the pairs the MFMA range scan rescored
-    // with the canonical key (kRangeMfmaExactWord; cumulative, a clear keeps it)
+    // with the canonical key (kRangeMfmaExactWord; cumulative, a clear keeps it), [232, 240) the pairs
+    // an encode decided in fp64 (kEncodeExactWord; likewise)
     if (e == hipSuccess) e = hipMalloc(&ix->d_xmax, kXmaxBytes);
     if (e == hipSuccess) e = zero_now(ix->d_xmax, kXmaxBytes, ix->stream);
     if (e == hipSuccess) e = hipMalloc(&ix->d_i8, 64);
@@ -1193,6 +1201,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "code_dot_mfma must be 0 (auto), 1 (whenever eligible) or 2 (never)");
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->code_dot_mfma = value;
+    } else if (n == "encode_mfma") {
+        if (!encode_knob_ok(value))
+            return set_error(VDB_ERR_INVALID, "encode_mfma must be 0 (the MFMA kernel and the undecided pass) or 2 (every pair in fp64)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->encode_mfma = value;
     } else if (n == "jaccard_mfma") {
         if (!jaccard_knob_ok(value))
             return set_error(VDB_ERR_INVALID, "jaccard_mfma must be 0 (auto), 1 (whenever eligible) or 2 (never)");
@@ -1388,6 +1401,17 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "code_dot_queries") *value = ix->n_code_dot_queries.load();
     else if (n == "code_dot_mfma_searches") *value = ix->n_code_dot_mfma_searches.load();
     else if (n == "code_dot_mfma_queries") *value = ix->n_code_dot_mfma_queries.load();
+    else if (n == "encode_calls") *value = ix->n_encode_calls.load();
+    else if (n == "encode_vectors") *value = ix->n_encode_vectors.load();
+    else if (n == "encode_pairs") *value = ix->n_encode_pairs.load();
+    else if (n == "encode_exact_pairs") {  // counted by the undecided pass: after the calls queued so far
+        HIP_TRY(hipSetDevice(ix->device));
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+        unsigned long long c = 0;
+        HIP_TRY(hipMemcpy(&c, ix->d_xmax + kEncodeExactWord, sizeof(c), hipMemcpyDeviceToHost));
+        *value = (int64_t)c;
+    }
     else if (n == "jaccard_searches") *value = ix->n_jaccard_searches.load();
     else if (n == "jaccard_queries") *value = ix->n_jaccard_queries.load();
     else if (n == "jaccard_mfma_searches") *value = ix->n_jaccard_mfma_searches.load();
@@ -4030,6 +4054,26 @@ int32_t vdb_index_search_hybrid_sum(vdb_index* ix, const float* queries, const i
     return VDB_OK;
 }
 
+namespace {
+
+// Room for a code column of n rows of n_bytes bytes (the tiled layout of vdb_hamming_plan.h); the column
+// counts as detached until the caller has filled it.  Under the exclusive lock, the index idle.
+int code_column_reserve(vdb_index* ix, int64_t n, int n_bytes) {
+    const int64_t words = ham_packed_words(n, ham_words(n_bytes));
+    if (words > ix->code_cap_words || !ix->codes) {
+        uint64_t* cnew = nullptr;
+        const int64_t cap = std::max<int64_t>(words, 64);
+        HIP_TRY(hipMalloc(&cnew, (size_t)cap * sizeof(uint64_t)));
+        if (ix->codes) (void)hipFree(ix->codes);
+        ix->codes = cnew;
+        ix->code_cap_words = cap;
+    }
+    ix->code_set = false;  // until the new column is whole
+    return VDB_OK;
+}
+
+}  // namespace
+
 int32_t vdb_index_set_codes(vdb_index* ix, const uint8_t* codes, int64_t n, int32_t n_bytes, int32_t mem, void* stream) {
     if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
     if (mem != VDB_MEM_HOST && mem != VDB_MEM_DEVICE) return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
@@ -4054,16 +4098,10 @@ int32_t vdb_index_set_codes(vdb_index* ix, const uint8_t* codes, int64_t n, int3
         return VDB_OK;
     }
     hipStream_t st = ix->stream;
-    const int64_t words = ham_packed_words(n, ham_words(n_bytes));
-    if (words > ix->code_cap_words || !ix->codes) {
-        uint64_t* cnew = nullptr;
-        const int64_t cap = std::max<int64_t>(words, 64);
-        HIP_TRY(hipMalloc(&cnew, (size_t)cap * sizeof(uint64_t)));
-        if (ix->codes) (void)hipFree(ix->codes);
-        ix->codes = cnew;
-        ix->code_cap_words = cap;
+    {
+        const int rc = code_column_reserve(ix, n, n_bytes);
+        if (rc) return rc;
     }
-    ix->code_set = false;  // until the new column is whole
     if (n > 0) {
         const uint8_t* src = codes;
         uint8_t* up = nullptr;
@@ -4088,6 +4126,182 @@ int32_t vdb_index_set_codes(vdb_index* ix, const uint8_t* codes, int64_t n, int3
     ix->code_bytes = n_bytes;
     ix->code_set = true;
     ix->n_code_sets++;
+    return VDB_OK;
+}
+
+namespace {
+
+// The validation both encode calls share: every cause before anything is launched.
+int encode_check(const vdb_index* ix, int64_t n, int32_t n_bits, bool has_proj, int32_t mem, bool io_ok) {
+    switch (encode_validate(n, ix->dim, n_bits, has_proj, mem, io_ok)) {
+        case kEncBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+        case kEncBadBits: return set_error(VDB_ERR_INVALID, "n_bits must be in [1, %d], got %d", kEncMaxBits, n_bits);
+        case kEncIdentityWidth:
+            return set_error(VDB_ERR_INVALID, "a NULL projection is the identity: n_bits must be the dim %d, got %d", ix->dim, n_bits);
+        case kEncBadCount: return set_error(VDB_ERR_INVALID, "n must be in [0, %lld], got %lld", (long long)kEncMaxVectors, (long long)n);
+        case kEncNullPointer: return set_error(VDB_ERR_INVALID, "NULL vectors/out_codes pointer");
+        default: return VDB_OK;
+    }
+}
+
+// Queue an encode's kernels on st.  dev: the scratch sc carves; vectors: the call's own [n][dim] rows in
+// device memory, or NULL for the index's rows; proj / thr: device memory (NULL: identity / zeros).
+int encode_launch(vdb_index* ix, const EncodeScratch& sc, char* dev, const float* vectors, int64_t n, const float* proj,
+                  const double* thr, int n_bits, uint8_t* out, hipStream_t st) {
+    EncodeArgs a{};
+    a.n = n;
+    a.D = ix->dim;
+    a.Dp = ix->Dp;
+    a.n_bits = n_bits;
+    a.n_bytes = sc.n_bytes;
+    a.stride = sc.stride;
+    a.thr = thr;
+    a.out = out;
+    a.exact_pairs = ix->d_xmax + kEncodeExactWord;
+    if (!proj) {  // the identity projection: the rows where they are
+        a.V = vectors ? vectors : ix->X;
+        a.ldv = vectors ? ix->dim : ix->Dp;
+        HIP_TRY(launch_encode_sign(a, st));
+        return VDB_OK;
+    }
+    float* pw = reinterpret_cast<float*>(dev + sc.pw);
+    double* pn = reinterpret_cast<double*>(dev + sc.pn);
+    HIP_TRY(launch_encode_prep(proj, n_bits, sc.pad_bits, ix->dim, ix->Dp, pw, pn, st));
+    a.P = pw;
+    a.pn = pn;
+    a.V = ix->X;
+    a.xn = ix->nrm64;
+    a.ldv = ix->Dp;
+    if (vectors) {
+        float* vw = reinterpret_cast<float*>(dev + sc.vw);
+        double* xn = reinterpret_cast<double*>(dev + sc.xn);
+        HIP_TRY(launch_encode_prep(vectors, n, n, ix->dim, ix->Dp, vw, xn, st));
+        a.V = vw;
+        a.xn = xn;
+    }
+    const bool all = ix->encode_mfma == 2;
+    if (!all) {
+        a.cw = reinterpret_cast<uint32_t*>(dev + sc.cw);
+        a.uw = reinterpret_cast<uint32_t*>(dev + sc.uw);
+        HIP_TRY(launch_encode_gemm(a, st));
+    }
+    HIP_TRY(launch_encode_drain(a, all, ix->n_cu, st));
+    return VDB_OK;
+}
+
+}  // namespace
+
+int32_t vdb_index_encode_codes(vdb_index* ix, const float* proj, const double* thresholds, int32_t n_bits, int32_t mem,
+                               void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::shared_mutex> g(ix->mu);
+    const int64_t n = ix->count;
+    {
+        const int rc = encode_check(ix, n, n_bits, proj != nullptr, mem, true);
+        if (rc) return rc;
+    }
+    // queued device-memory searches on caller streams read the column this call replaces
+    {
+        const int wr = wait_idle(ix);
+        if (wr) return wr;
+    }
+    hipStream_t st = ix->stream;
+    const int n_bytes = enc_bytes(n_bits);
+    {
+        const int rc = code_column_reserve(ix, n, n_bytes);
+        if (rc) return rc;
+    }
+    if (n > 0) {
+        const bool host = mem == VDB_MEM_HOST;
+        const EncodeScratch sc = encode_scratch(n, ix->dim, ix->Dp, n_bits, proj != nullptr, thresholds != nullptr, host,
+                                                false, proj != nullptr && ix->encode_mfma == 0, true);
+        char* dev = nullptr;
+        HIP_TRY(hipMalloc(&dev, (size_t)sc.total));
+        hipError_t e = hipSuccess;
+        const float* pd = proj;
+        const double* td = thresholds;
+        if (host) {
+            if (proj) {
+                e = hipMemcpyAsync(dev + sc.proj, proj, (size_t)n_bits * ix->dim * 4, hipMemcpyHostToDevice, st);
+                pd = reinterpret_cast<const float*>(dev + sc.proj);
+            }
+            if (e == hipSuccess && thresholds) {
+                e = hipMemcpyAsync(dev + sc.thr, thresholds, (size_t)n_bits * 8, hipMemcpyHostToDevice, st);
+                td = reinterpret_cast<const double*>(dev + sc.thr);
+            }
+        } else {
+            // the projection may still be being written on the caller's stream
+            e = order_after_caller(st, stream);
+        }
+        int rc = VDB_OK;
+        if (e == hipSuccess) rc = encode_launch(ix, sc, dev, nullptr, n, pd, td, n_bits, reinterpret_cast<uint8_t*>(dev + sc.out), st);
+        if (e == hipSuccess && rc == VDB_OK)
+            e = launch_hamming_pack(reinterpret_cast<const uint8_t*>(dev + sc.out), n, n_bytes, ix->codes, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        (void)hipFree(dev);
+        if (rc) return rc;
+        HIP_TRY(e);
+        HIP_TRY(es);
+    }
+    ix->code_n = n;
+    ix->code_bytes = n_bytes;
+    ix->code_set = true;
+    ix->n_code_sets++;
+    ix->n_encode_calls++;
+    ix->n_encode_vectors += n;
+    ix->n_encode_pairs += n * n_bits;
+    return VDB_OK;
+}
+
+int32_t vdb_index_encode(vdb_index* ix, const float* vectors, int64_t n, const float* proj, const double* thresholds,
+                         int32_t n_bits, int32_t mem, uint8_t* out_codes, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    {
+        const int rc = encode_check(ix, n, n_bits, proj != nullptr, mem, vectors != nullptr && out_codes != nullptr);
+        if (rc) return rc;
+    }
+    if (n == 0) return VDB_OK;
+    const bool host = mem == VDB_MEM_HOST;
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+    const int dim = ix->dim;
+    const EncodeScratch sc = encode_scratch(n, dim, ix->Dp, n_bits, proj != nullptr, thresholds != nullptr, host, true,
+                                            proj != nullptr && ix->encode_mfma == 0, false);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    const float* vd = vectors;
+    const float* pd = proj;
+    const double* td = thresholds;
+    uint8_t* od = out_codes;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the bytes come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.vec - sc.in0), vectors, (size_t)n * dim * 4);
+            if (proj) std::memcpy(h + (sc.proj - sc.in0), proj, (size_t)n_bits * dim * 4);
+            if (thresholds) std::memcpy(h + (sc.thr - sc.in0), thresholds, (size_t)n_bits * 8);
+        });
+        if (rc) return rc;
+        vd = reinterpret_cast<const float*>(dev + sc.vec);
+        pd = proj ? reinterpret_cast<const float*>(dev + sc.proj) : nullptr;
+        td = thresholds ? reinterpret_cast<const double*>(dev + sc.thr) : nullptr;
+        od = reinterpret_cast<uint8_t*>(dev + sc.out);
+    }
+    rc = encode_launch(ix, sc, dev, vd, n, pd, td, n_bits, od, st);
+    if (rc) return rc;
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_codes, r, (size_t)sc.out_bytes);
+    }
+    ix->n_encode_calls++;
+    ix->n_encode_vectors += n;
+    ix->n_encode_pairs += n * n_bits;
     return VDB_OK;
 }
 

@@ -497,6 +497,26 @@ hipError_t launch_hybrid_sets(int64_t* offs, double* weights, int n_queries, dou
 // vdb_index_search_hamming).  Pack: codes [n][n_bytes] row-major bytes in device memory -> packed
 // [ceil(n / 64)][W][64] 64-bit words (vdb_hamming_plan.h), pad bytes and pad rows zero.
 hipError_t launch_hamming_pack(const uint8_t* codes, int64_t n, int n_bytes, uint64_t* packed, hipStream_t st);
+// Codes from vectors (vdb_encode.hip, vdb_index_encode_codes / vdb_index_encode; vdb_encode_plan.h):
+// bit j of vector r is 1 iff the canonical fp64 dot of P[j] and V[r] is > thr[j] (thr NULL: zeros).
+// V [n] rows of ldv floats, P [n_bits rounded up to 32][Dp] and the norms xn [n] / pn in device memory;
+// out [n][n_bytes] row-major code bytes, pad bits 0.  Prep: a row-major [n][D] source into zero-padded
+// [n_pad][Dp] rows with their canonical norms.  Gemm: the pairs the margin decides, as 32-bit words into
+// cw (certain ones) and uw (undecided) [n][stride]; needs ldv == Dp.  Drain: the undecided pairs in
+// fp64 (counted into *exact_pairs) and the bytes to out; `all`: every pair, cw / uw not read.  Sign:
+// the identity projection (n_bits == D; P, the norms and the word buffers unused; ldv >= D).
+struct EncodeArgs {
+    const float* V; int64_t n; int64_t ldv; const double* xn;
+    const float* P; const double* pn; const double* thr;
+    int D; int Dp; int n_bits; int n_bytes; int stride;
+    uint32_t* cw; uint32_t* uw; uint8_t* out;
+    unsigned long long* exact_pairs;
+};
+hipError_t launch_encode_prep(const float* src, int64_t n, int64_t n_pad, int D, int Dp, float* dst, double* nrm,
+                              hipStream_t st);
+hipError_t launch_encode_gemm(const EncodeArgs& a, hipStream_t st);
+hipError_t launch_encode_drain(const EncodeArgs& a, bool all, int n_cu, hipStream_t st);
+hipError_t launch_encode_sign(const EncodeArgs& a, hipStream_t st);
 // Search: queries [n_queries][n_bytes] bytes in device memory (any bytes are a query).  Row r < N
 // is a candidate when mask (optional, the row_mask layout) has its bit; the best k by (distance asc,
 // row asc) go to out_d / out_i [b * k + e], distance -1 / index -1 behind them.  Grid (n_seg, query

@@ -58,7 +58,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_set_column", "vdb_index_filter_mask",
     "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim",
     "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_index_search_hybrid_sum",
-    "vdb_index_set_codes", "vdb_index_search_hamming", "vdb_index_search_hamming_range", "vdb_index_search_code_dot", "vdb_index_search_jaccard", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_codes", "vdb_index_search_hamming", "vdb_index_search_hamming_range", "vdb_index_search_code_dot", "vdb_index_search_jaccard", "vdb_index_encode_codes", "vdb_index_encode", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -150,6 +150,8 @@ def load_library():
             "vdb_index_search_jaccard": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_index_search_hamming_range": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64,
                                                        c_vp]),
+            "vdb_index_encode_codes": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+            "vdb_index_encode": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
             "vdb_similarity_matrix": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_normalize_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
@@ -892,6 +894,59 @@ class NativeIndex:
         queued on ``stream``."""
         _check(self._lib.vdb_index_set_codes(self._h, ctypes.c_void_p(codes_ptr or None), int(n), int(n_bytes), MEM_DEVICE,
                                              ctypes.c_void_p(stream or None)))
+
+    def _quantizer(self, proj, thresholds, n_bits):
+        """(proj fp32 [n_bits, dim] or None, thresholds fp64 [n_bits] or None, n_bits) as the encode calls
+        take them; only shapes are checked here, the library checks the rest."""
+        P = None if proj is None else np.ascontiguousarray(proj, dtype=np.float32)
+        if P is not None and (P.ndim != 2 or P.shape[1] != self.dim):
+            raise ValueError(f"proj must be [n_bits, {self.dim}], got shape {P.shape}")
+        nb = int(n_bits) if n_bits is not None else (P.shape[0] if P is not None else self.dim)
+        if P is not None and P.shape[0] != nb:
+            raise ValueError(f"proj has {P.shape[0]} rows, n_bits is {nb}")
+        t = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        if t is not None and t.shape != (nb,):
+            raise ValueError(f"thresholds must be [{nb}], got shape {t.shape}")
+        return P, t, nb
+
+    def encode_codes(self, proj=None, thresholds=None, n_bits: Optional[int] = None) -> None:
+        """include/vdb.h vdb_index_encode_codes, host memory: derive the code column from the stored rows
+        on the device and attach it as ``set_codes`` would.  Bit j of a row x is 1 iff the canonical fp64
+        dot of ``proj[j]`` (fp32 ``[n_bits, dim]``; None = the identity, ``n_bits == dim``) and x is >
+        ``thresholds[j]`` (fp64, None = zeros).  A call the library refuses raises ValueError."""
+        P, t, nb = self._quantizer(proj, thresholds, n_bits)
+        _check(self._lib.vdb_index_encode_codes(self._h, _ptr(P) if P is not None else None,
+                                                _ptr(t) if t is not None else None, nb, MEM_HOST, None))
+
+    def encode(self, vectors, proj=None, thresholds=None, n_bits: Optional[int] = None) -> np.ndarray:
+        """include/vdb.h vdb_index_encode, host memory: ``vectors`` fp32 ``[n, dim]`` encoded by the rule
+        of ``encode_codes``; returns uint8 ``[n, ceil(n_bits / 8)]`` (bit j = bit j % 8 of byte j // 8).
+        The index's rows are not read."""
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim == 1:
+            v = v.reshape(1, -1)
+        if v.ndim != 2 or v.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [n, {self.dim}], got shape {v.shape}")
+        P, t, nb = self._quantizer(proj, thresholds, n_bits)
+        out = np.empty((v.shape[0], max(nb + 7, 0) // 8), dtype=np.uint8)
+        _check(self._lib.vdb_index_encode(self._h, _ptr(v), v.shape[0], _ptr(P) if P is not None else None,
+                                          _ptr(t) if t is not None else None, nb, MEM_HOST, _ptr(out), None))
+        return out
+
+    def encode_codes_device(self, proj_ptr: int, thresholds_ptr: int, n_bits: int, stream: int = 0) -> None:
+        """vdb_index_encode_codes with a device-memory projection and thresholds (0 = none), read after the
+        work queued on ``stream``."""
+        _check(self._lib.vdb_index_encode_codes(self._h, ctypes.c_void_p(proj_ptr or None),
+                                                ctypes.c_void_p(thresholds_ptr or None), int(n_bits), MEM_DEVICE,
+                                                ctypes.c_void_p(stream or None)))
+
+    def encode_device(self, vectors_ptr: int, n: int, proj_ptr: int, thresholds_ptr: int, n_bits: int, out_codes_ptr: int,
+                      stream: int = 0) -> None:
+        """vdb_index_encode with device-memory arguments; stream-ordered, nothing is read back."""
+        _check(self._lib.vdb_index_encode(
+            self._h, ctypes.c_void_p(vectors_ptr or None), int(n), ctypes.c_void_p(proj_ptr or None),
+            ctypes.c_void_p(thresholds_ptr or None), int(n_bits), MEM_DEVICE, ctypes.c_void_p(out_codes_ptr or None),
+            ctypes.c_void_p(stream or None)))
 
     def search_hamming(self, queries, k: int, mask: Optional[np.ndarray] = None, index_offset: int = 0):
         """include/vdb.h vdb_index_search_hamming, host memory: ``queries`` uint8 ``[B, n_bytes]`` of

@@ -110,6 +110,8 @@ def _sparse_pair(value, what: str):
 # binary_query: the most rows per query and the widest code (include/vdb.h vdb_index_search_hamming)
 BINARY_MAX_K = 1024
 BINARY_MAX_BYTES = 1024
+# configure_quantizer: the widest code a quantizer derives (csrc/vdb_encode_plan.h kEncMaxBits)
+QUANTIZER_MAX_BITS = 8192
 
 
 def normalize_code(value, what: str) -> np.ndarray:
@@ -470,6 +472,11 @@ class MLXVectorStore:
         self._code_mask: Optional[np.ndarray] = None
         self._code_bytes = 0
         self._code_sets = -1
+        # quantized_query: the quantizer (configure_quantizer; in memory only): its id (bumped by every
+        # configure), kind, projection fp32 [n_bits, dim] (None = the identity) and thresholds fp64
+        self._quantizer: Optional[Dict[str, Any]] = None
+        self._quantizer_ids = 0
+        self._quantizer_lock = threading.Lock()  # ensure_quantizer: one first configuration (taken before the others)
         # range filters: metadata key -> (slot, (rows, update count, metadata version), exact) for the numeric columns
         # attached to the index's 16 slots, least recently used first, and the index's
         # "column_sets" after the last attach made here
@@ -1478,6 +1485,124 @@ class MLXVectorStore:
                     out.append((ib, dist[b][valid].astype(np.int64).tolist(), [meta[i] if i < len(meta) else {} for i in ib]))
                 return out
             # rescoring: the fetched ids, sorted, are each query's row list of the exact subset search
+            lists = [np.sort(idx[b][idx[b] >= 0]) for b in range(B)]
+            scores, ridx = self._index.search_rows(R, k, lists)
+            for b in range(B):
+                valid = ridx[b] >= 0
+                ib = ridx[b][valid].tolist()
+                d_of = dict(zip(idx[b].tolist(), dist[b].tolist()))
+                out.append((ib, [int(d_of[i]) for i in ib], [meta[i] if i < len(meta) else {} for i in ib],
+                            scores[b][valid].astype(np.float64).tolist()))
+            return out
+
+    # ---- quantized query ----------------------------------------------------------------
+    def configure_quantizer(self, kind: str = "sign", n_bits: Optional[int] = None, center: bool = True, seed: int = 0) -> Dict:
+        """Choose how ``quantized_query`` turns the stored rows and its queries into binary codes on the
+        device (include/vdb.h vdb_index_encode_codes): bit j is 1 iff p_j . x > t_j in canonical fp64.
+        ``"sign"``: the identity projection, ``n_bits`` = dim.  ``"simhash"``: ``n_bits`` rows drawn from
+        ``np.random.default_rng(seed).standard_normal((n_bits, dim), float32)``.  ``center=True`` freezes
+        mu, the fp64 mean of the rows present now, and sets t = P mu in fp64 (t = mu for ``"sign"``);
+        otherwise t = 0.  The configuration lives in memory only -> {"kind", "n_bits", "centered"}."""
+        if kind not in ("sign", "simhash"):
+            raise ValueError(f"kind must be 'sign' or 'simhash', got {kind!r}")
+        if len(self._devices()) > 1:
+            raise NotImplementedError("quantized query is not supported on a multi-device store")
+        with _Read(self._rw):
+            dim = self._dim
+            if not dim:
+                raise ValueError("the store is empty: a quantizer needs the dim (add vectors first)")
+            if kind == "sign":
+                if n_bits is not None and int(n_bits) != dim:
+                    raise ValueError(f"'sign' has one bit per dim: n_bits must be {dim}, got {n_bits}")
+                bits, P = dim, None
+            else:
+                bits = int(n_bits) if n_bits is not None else dim
+                if not 1 <= bits <= QUANTIZER_MAX_BITS:
+                    raise ValueError(f"n_bits must be in [1, {QUANTIZER_MAX_BITS}], got {bits}")
+                P = np.random.default_rng(seed).standard_normal((bits, dim), dtype=np.float32)
+            t = None
+            if center and self._vector_count:
+                mu = self._index.get_vectors(0, self._vector_count).astype(np.float64).mean(axis=0)
+                t = mu if P is None else P.astype(np.float64) @ mu
+            with self._code_lock:
+                self._quantizer_ids += 1
+                self._quantizer = {"id": self._quantizer_ids, "kind": kind, "n_bits": bits, "proj": P, "thresholds": t}
+            return {"kind": kind, "n_bits": bits, "centered": t is not None}
+
+    def has_quantizer(self) -> bool:
+        return self._quantizer is not None
+
+    def ensure_quantizer(self, kind: str = "sign", n_bits: Optional[int] = None, center: bool = True, seed: int = 0) -> bool:
+        """``configure_quantizer`` with these arguments unless the store has a quantizer already -> whether
+        this call configured it.  Concurrent first callers configure once: the others wait and keep the
+        first's quantizer, whatever their own arguments."""
+        with self._quantizer_lock:
+            if self._quantizer is not None:
+                return False
+            self.configure_quantizer(kind, n_bits, center, seed)
+            return True
+
+    def _attach_quantized(self, qz: Dict) -> None:
+        """Make the codes the quantizer derives from the stored rows the attached code column (read lock
+        and _code_lock held).  The tag shares ``_attach_codes``' slot, so metadata codes and derived
+        codes displace each other."""
+        n = self._vector_count
+        tag = (("quantizer", qz["id"]), n, self._index.stat("rows_updated"))
+        if self._code_tag == tag and self._index.stat("code_rows") == n \
+                and self._index.stat("code_sets") == self._code_sets:
+            return
+        self._code_tag = None
+        self._index.encode_codes(qz["proj"], qz["thresholds"], qz["n_bits"])
+        self._code_tag, self._code_bytes, self._code_mask = tag, (qz["n_bits"] + 7) // 8, None
+        self._code_sets = self._index.stat("code_sets")
+
+    def quantized_query(self, vector, k: int = 10, filter_metadata: Optional[Dict] = None, oversample: int = 4,
+                        rescore: bool = True) -> Tuple:
+        """Binary-quantised search of the dense rows: the store derives one code per row on the device
+        by the configured quantizer (``configure_quantizer``; re-derived when rows were added, removed
+        or updated), encodes ``vector`` by the same rule, fetches the min(k * oversample, 1024) rows
+        nearest in Hamming distance and returns the exact dense top-k of that set -> (indices, distances,
+        metadata, scores), best dense score first.  ``rescore=False`` returns the k Hamming-nearest rows
+        -> (indices, distances, metadata).  The reference has no such read."""
+        return self.batch_quantized_query([vector], k, filter_metadata, oversample, rescore)[0]
+
+    def batch_quantized_query(self, vectors, k: int = 10, filter_metadata: Optional[Dict] = None, oversample: int = 4,
+                              rescore: bool = True) -> List[Tuple]:
+        """``quantized_query`` for a list of vectors from one encode and one search: one tuple per query."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("quantized query is not supported on a multi-device store")
+        k, oversample = int(k), int(oversample)
+        if not 1 <= k <= BINARY_MAX_K:
+            raise ValueError(f"k must be in [1, {BINARY_MAX_K}], got {k}")
+        if oversample < 1:
+            raise ValueError(f"oversample must be >= 1, got {oversample}")
+        qz = self._quantizer
+        if qz is None:
+            raise ValueError("no quantizer is configured (configure_quantizer)")
+        B = len(vectors)
+        R = np.stack([np.asarray(_as_matrix(v), dtype=np.float32).reshape(-1) for v in vectors]) if B else None
+        empty = [([], [], [], []) if rescore else ([], [], []) for _ in range(B)]
+        with _Read(self._rw):
+            if self._vector_count == 0 or B == 0:
+                return empty
+            if R.shape[1] != self._dim:
+                raise ValueError(f"Dimension mismatch: query has {R.shape[1]} dims, store holds {self._dim}")
+            mask = self._sparse_mask(filter_metadata)
+            if mask is False:
+                return empty
+            fetch = min(k * oversample, BINARY_MAX_K) if rescore else k
+            with self._code_lock:  # one attached column: attach and search as one step
+                self._attach_quantized(qz)
+                codes = self._index.encode(R, qz["proj"], qz["thresholds"], qz["n_bits"])
+                dist, idx = self._index.search_hamming(codes, fetch, mask=mask)
+            meta = self._metadata
+            out = []
+            if not rescore:
+                for b in range(B):
+                    valid = idx[b] >= 0
+                    ib = idx[b][valid].tolist()
+                    out.append((ib, dist[b][valid].astype(np.int64).tolist(), [meta[i] if i < len(meta) else {} for i in ib]))
+                return out
             lists = [np.sort(idx[b][idx[b] >= 0]) for b in range(B)]
             scores, ridx = self._index.search_rows(R, k, lists)
             for b in range(B):
