@@ -177,7 +177,10 @@ int32_t vdb_index_reserve(vdb_index* idx, int64_t rows);
  * its stats "code_dot_searches", "code_dot_queries", "code_dot_mfma_searches", "code_dot_mfma_queries"
  * are described there) and "jaccard_mfma" (which kernel vdb_index_search_jaccard takes: 0 = auto, 1 =
  * the MFMA one whenever eligible, 2 = never; its stats "jaccard_searches", "jaccard_queries",
- * "jaccard_mfma_searches", "jaccard_mfma_queries" are described there).  The numeric columns and predicate masks have no
+ * "jaccard_mfma_searches", "jaccard_mfma_queries" are described there) and "jaccard_range_mfma" (which
+ * scan vdb_index_search_jaccard_range takes: 0 = auto, 1 = the MFMA one for every call, 2 = never; its
+ * stats "jaccard_range_searches", "jaccard_range_queries", "jaccard_range_mfma_searches",
+ * "jaccard_range_mfma_queries" are described there).  The numeric columns and predicate masks have no
  * knob; their stats "column_slots", "column_sets", "filter_calls", "filter_preds" are described at
  * vdb_index_filter_mask.  Stats also: "searches", "queries",
  * "fallback_queries", "overflow_queries", "inconsistent_queries", "repass_queries",
@@ -915,6 +918,53 @@ int32_t vdb_index_search_hamming_range(vdb_index* idx, const uint8_t* queries, i
                                        const int32_t* radii, const uint32_t* row_mask, int32_t mem,
                                        int64_t cap, int64_t* out_counts, int64_t* out_indices,
                                        int32_t* out_distances, int64_t index_offset, void* stream);
+
+/* vdb_index_search_jaccard_range: every row whose Jaccard / Tanimoto similarity with a query code is at
+ * or above that query's threshold, with exact counts -- "every compound with Tanimoto >= 0.7 to this
+ * fingerprint" and "how many are there" (chemfp's threshold search, RDKit's BulkTanimotoSimilarity with
+ * a cut-off, Milvus' range_search on BIN_FLAT / JACCARD).  Top-k cannot answer these, and a Hamming
+ * radius is no substitute: the similarity depends on each row's own popcount.
+ *   queries      [n_queries, n_bytes] uint8, of the attached width; 0 <= n_queries <= 65 535
+ *   thr_num, thr_den [n_queries] int32: the threshold of query b is the exact rational thr_num[b] /
+ *                thr_den[b], 1 <= den <= 2^18, 0 <= num <= den.  The similarities of an n-bit column are
+ *                the fractions of denominator <= n <= 8 192, so any real threshold t is equivalent to the
+ *                smallest such fraction >= t; a rational keeps the decision free of division and rounding.
+ *   cap          slots per query, >= 0, n_queries * cap <= 2^36; 0 = count only (the three list
+ *                pointers may then be NULL)
+ *   out_counts   [n_queries] int64, required; out_indices [n_queries, cap] int64; out_inter, out_union
+ *                [n_queries, cap] int32
+ *   row_mask, mem, index_offset, stream: as vdb_index_search_hamming; all pointers of one memory kind.
+ * Contract: i = popcount(q_b AND x_r), u = popcount(q_b OR x_r); u == 0 (both empty) is tested as i = u =
+ * 1, similarity 1, vdb_index_search_jaccard's convention.  Row r passes query b when its mask bit is
+ * set, r < count and i * den >= num * u: equality passes, num == 0 passes every eligible row.  Both
+ * products are at most 8 192 * 2^18 = 2^31.  out_counts[b] is the exact number of passing rows, also when
+ * it exceeds cap.  The first min(count, cap) passing rows are written in ascending row id, out_indices =
+ * row + index_offset, out_inter = i and out_union = u as the raw popcounts (0 / 0 for two empty sets);
+ * later slots up to cap hold -1 / -1 / -1; nothing at or past cap is written.  The result is integers
+ * and the same bytes for every metric, precision setting, memory kind and scan.  Errors, before anything
+ * is launched, both memory kinds, all VDB_ERR_INVALID: no column attached, n_queries out of range, a bad
+ * cap, a bad mem, a NULL queries / thr_num / thr_den / out_counts with n_queries > 0, NULL list pointers
+ * with cap > 0; host-memory calls also reject a threshold outside the bounds above (no stat moves).
+ * Device-memory calls read nothing back and are stream-ordered; a threshold outside the bounds there
+ * gives that query a count of 0 and -1 in all its slots.  n_queries == 0 is VDB_OK; an empty index with
+ * an empty column attached gives counts of 0.  Locking, workspace, pinned staging and stream ordering
+ * are vdb_index_search_hamming_range's.
+ * Two scans fill the hit bitmap the dense range search's prefix and emit kernels finish, with the same
+ * result in every byte: AND + popcount with |x| counted once per row for a block of up
+ * to 16 queries and one ballot per (tile, query); and the int8 matrix instruction in blocks of 64, bits
+ * as 0 / 1 on both sides so that an accumulator holds i, where a lane forms u, does the two 32-bit
+ * multiplies and the compare for its 16 rows and one exchange with lane ^ 32 completes a bitmap word.
+ * Knob "jaccard_range_mfma": 0 = auto (the default: calls of at least 64 queries take the second, a
+ * measured threshold), 1 = the second for every call, 2 = never; any other value is VDB_ERR_INVALID.  Stats, cumulative over successful calls: "jaccard_range_searches",
+ * "jaccard_range_queries", and "jaccard_range_mfma_searches", "jaccard_range_mfma_queries" for those the
+ * second scan served; "jaccard_*", "hamming_*", "hamming_range_*", "searches", "queries" and every
+ * "searches_*" stat stay still. */
+int32_t vdb_index_search_jaccard_range(vdb_index* idx, const uint8_t* queries, int32_t n_queries,
+                                       const int32_t* thr_num, const int32_t* thr_den,
+                                       const uint32_t* row_mask, int32_t mem,
+                                       int64_t cap, int64_t* out_counts, int64_t* out_indices,
+                                       int32_t* out_inter, int32_t* out_union,
+                                       int64_t index_offset, void* stream);
 
 /* Encoding on the device: the code column derived from the stored rows, and query vectors encoded by
  * the same rule -- binary quantisation of the dense embeddings (Qdrant / Weaviate BQ, Elasticsearch

@@ -200,6 +200,23 @@ class VectorBinaryRangeQuery(BaseModel):
     limit: int = Field(default=1000, ge=1, le=100000, description="Most results returned per query (the nearest ones)")
 
 
+class VectorBinaryJaccardRangeQuery(BaseModel):
+    """Every row whose binary code (stored in the row's metadata under ``binary_key``, as hex), taken as
+    a set of bits, has a Jaccard / Tanimoto similarity of at least ``threshold`` with ``code`` (single) or
+    with each of ``codes`` (batch), most similar first, at most ``limit`` per query; the exact number of
+    matches comes with them.  ``threshold`` is a number in [0, 1] or an exact ``[num, den]`` pair of
+    integers.  The store checks the rest (one code width, the threshold's bounds); a value outside that
+    is a 400."""
+    user_id: str
+    model_id: str
+    code: Optional[str] = Field(default=None, description="The query's code, hex")
+    codes: Optional[List[str]] = Field(default=None, description="A batch of query codes, hex")
+    threshold: Union[float, List[int]] = Field(..., description="Smallest similarity of a match: a number in [0, 1] or [num, den]")
+    filter_metadata: Optional[Dict[str, Any]] = Field(default=None, description="Metadata filter")
+    binary_key: str = Field(default="code", description="Metadata key holding each row's code")
+    limit: int = Field(default=1000, ge=1, le=100000, description="Most results returned per query (the most similar ones)")
+
+
 class VectorHybridQuery(BaseModel):
     """Dense and sparse retrieval fused by weighted reciprocal rank: the best ``fetch_k`` rows (null:
     min(200, max(k, 4 k))) for ``query`` and the best ``fetch_k`` for ``sparse`` are fused per row,
@@ -389,6 +406,19 @@ class VectorBinaryRangeQueryResponse(BaseModel):
     # nearest first: {"metadata", "distance" (Hamming, an integer), "rank"}; total_matches is the exact
     # number of rows within the radius and may exceed len(results).  A batch request answers with
     # "batch_results" and "batch_total_matches", one entry per code.
+    results: List[Dict[str, Any]]
+    total_matches: int
+    batch_results: Optional[List[List[Dict[str, Any]]]] = None
+    batch_total_matches: Optional[List[int]] = None
+    query_time_ms: float
+    total_vectors_searched: int
+
+
+class VectorBinaryJaccardRangeQueryResponse(BaseModel):
+    # most similar first: {"metadata", "intersection", "union" (the integers), "similarity" (intersection /
+    # union, 1.0 for two empty sets), "rank"}; total_matches is the exact number of rows at or above the
+    # threshold and may exceed len(results).  A batch request answers with "batch_results" and
+    # "batch_total_matches", one entry per code.
     results: List[Dict[str, Any]]
     total_matches: int
     batch_results: Optional[List[List[Dict[str, Any]]]] = None
@@ -957,6 +987,44 @@ def create_router(manager: Optional[VectorStoreManager] = None, auth: Callable =
         except Exception as e:
             logger.error("Error in binary range query: %s", e, exc_info=True)
             raise HTTPException(status_code=500, detail=f"Binary range query failed: {e}")
+
+    @router.post("/binary_jaccard_range_query", response_model=VectorBinaryJaccardRangeQueryResponse)
+    async def binary_jaccard_range_query_vectors(request: VectorBinaryJaccardRangeQuery, api_key: str = Depends(auth)):
+        """Every row with a Jaccard similarity of at least ``threshold``, most similar first, at most
+        ``limit`` of them; ``total_matches`` is the exact count.  ``code`` for one query, ``codes`` for a
+        batch.  A bad request (neither or both given, bad hex, a width other than the stored one, a
+        threshold outside its bounds: the store's ValueError) is a 400, an unsupported store a 501,
+        anything else a 500."""
+        t0 = time.time()
+        try:
+            store = await mgr.get_store(request.user_id, request.model_id)
+            if (request.code is None) == (request.codes is None):
+                raise HTTPException(status_code=400, detail="Give either code or codes")
+            codes = [request.code] if request.code is not None else request.codes
+            threshold = tuple(request.threshold) if isinstance(request.threshold, list) else request.threshold
+            loop = asyncio.get_running_loop()
+            got = await loop.run_in_executor(
+                mgr._executor, lambda: store.batch_binary_jaccard_range_query(codes, threshold,
+                                                                              filter_metadata=request.filter_metadata,
+                                                                              binary_key=request.binary_key, limit=request.limit))
+            shaped = [[dict(h, metadata=m, rank=i + 1) for i, (m, h) in enumerate(zip(t[2], t[1]))] for t in got]
+            totals = [t[3] for t in got]
+            single = request.code is not None
+            return VectorBinaryJaccardRangeQueryResponse(results=shaped[0] if single else [],
+                                                         total_matches=totals[0] if single else 0,
+                                                         batch_results=None if single else shaped,
+                                                         batch_total_matches=None if single else totals,
+                                                         query_time_ms=(time.time() - t0) * 1000,
+                                                         total_vectors_searched=store.get_stats().get("vector_count", 0))
+        except HTTPException:
+            raise
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Binary Jaccard range query failed: {e}")
+        except NotImplementedError as e:
+            raise HTTPException(status_code=501, detail=f"Binary Jaccard range query failed: {e}")
+        except Exception as e:
+            logger.error("Error in binary Jaccard range query: %s", e, exc_info=True)
+            raise HTTPException(status_code=500, detail=f"Binary Jaccard range query failed: {e}")
 
     @router.post("/hybrid_query", response_model=VectorHybridQueryResponse)
     async def hybrid_query_vectors(request: VectorHybridQuery, api_key: str = Depends(auth)):

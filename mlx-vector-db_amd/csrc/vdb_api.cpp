@@ -36,6 +36,7 @@
 #include "vdb_sparse_inv_plan.h"
 #include "vdb_hamming_plan.h"
 #include "vdb_hamming_range_plan.h"
+#include "vdb_jaccard_range_plan.h"
 #include "vdb_code_dot_plan.h"
 #include "vdb_jaccard_plan.h"
 #include "vdb_encode_plan.h"
@@ -340,6 +341,9 @@ struct vdb_index {
     int64_t jaccard_mfma = 0;  // knob: the int8-MFMA form of the Jaccard search (0 = by the batch size, 1 = whenever eligible, 2 = never)
     std::atomic<int64_t> n_jaccard_searches{0}, n_jaccard_queries{0};
     std::atomic<int64_t> n_jaccard_mfma_searches{0}, n_jaccard_mfma_queries{0};
+    int64_t jaccard_range_mfma = 0;  // knob: the scan of a Jaccard range search (0 = by the batch size, 1 = MFMA always, 2 = never)
+    std::atomic<int64_t> n_jaccard_range_searches{0}, n_jaccard_range_queries{0};
+    std::atomic<int64_t> n_jaccard_range_mfma_searches{0}, n_jaccard_range_mfma_queries{0};
     std::atomic<int64_t> n_hybrid_searches{0}, n_hybrid_queries{0};
     // vdb_index_search_hybrid_sum: calls and queries (successful calls)
     std::atomic<int64_t> n_hybsum_searches{0}, n_hybsum_queries{0};
@@ -1211,6 +1215,11 @@ int32_t vdb_index_set_param(vdb_index* ix, const char* name, int64_t value) {
             return set_error(VDB_ERR_INVALID, "jaccard_mfma must be 0 (auto), 1 (whenever eligible) or 2 (never)");
         std::unique_lock<std::shared_mutex> g(ix->mu);
         ix->jaccard_mfma = value;
+    } else if (n == "jaccard_range_mfma") {
+        if (!jaccard_range_knob_ok(value))
+            return set_error(VDB_ERR_INVALID, "jaccard_range_mfma must be 0 (auto), 1 (every call) or 2 (never)");
+        std::unique_lock<std::shared_mutex> g(ix->mu);
+        ix->jaccard_range_mfma = value;
     } else if (n == "hybrid_sum_wgs") {
         if (value < 0 || value > kHybsumMaxSeg)
             return set_error(VDB_ERR_INVALID, "hybrid_sum_wgs must be in [0, %d] (0 = auto)", kHybsumMaxSeg);
@@ -1416,6 +1425,10 @@ int32_t vdb_index_get_stat(const vdb_index* cix, const char* name, int64_t* valu
     else if (n == "jaccard_queries") *value = ix->n_jaccard_queries.load();
     else if (n == "jaccard_mfma_searches") *value = ix->n_jaccard_mfma_searches.load();
     else if (n == "jaccard_mfma_queries") *value = ix->n_jaccard_mfma_queries.load();
+    else if (n == "jaccard_range_searches") *value = ix->n_jaccard_range_searches.load();
+    else if (n == "jaccard_range_queries") *value = ix->n_jaccard_range_queries.load();
+    else if (n == "jaccard_range_mfma_searches") *value = ix->n_jaccard_range_mfma_searches.load();
+    else if (n == "jaccard_range_mfma_queries") *value = ix->n_jaccard_range_mfma_queries.load();
     else if (n == "hybrid_searches") *value = ix->n_hybrid_searches.load();
     else if (n == "hybrid_queries") *value = ix->n_hybrid_queries.load();
     else if (n == "hybrid_sum_searches") *value = ix->n_hybsum_searches.load();
@@ -4672,6 +4685,116 @@ int32_t vdb_index_search_hamming_range(vdb_index* ix, const uint8_t* queries, in
     if (mfma) {
         ix->n_hamming_range_mfma_searches++;
         ix->n_hamming_range_mfma_queries += B;
+    }
+    return VDB_OK;
+}
+
+int32_t vdb_index_search_jaccard_range(vdb_index* ix, const uint8_t* queries, int32_t B, const int32_t* thr_num,
+                                       const int32_t* thr_den, const uint32_t* row_mask, int32_t mem, int64_t cap,
+                                       int64_t* out_counts, int64_t* out_indices, int32_t* out_inter, int32_t* out_union,
+                                       int64_t index_offset, void* stream) {
+    if (!ix) return set_error(VDB_ERR_INVALID, "index is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> g(ix->mu);
+    const int64_t N = ix->count;
+    // everything checked before any launch (any bytes are a query; a device-memory call's thresholds are
+    // not read: the scans turn a bad one into "nothing passes")
+    const bool column = ix->code_set && ix->code_n == N;
+    int64_t at = 0;
+    switch (jaccard_range_validate(column, B, cap, mem, queries != nullptr, thr_num != nullptr, thr_den != nullptr,
+                                   out_counts != nullptr, out_indices != nullptr, out_inter != nullptr, out_union != nullptr,
+                                   thr_num, thr_den, &at)) {
+        case kJacRangeNoColumn: return set_error(VDB_ERR_INVALID, "no code column is attached (vdb_index_set_codes)");
+        case kJacRangeBadCount: return set_error(VDB_ERR_INVALID, "n_queries must be in [0, %d], got %d", kHamMaxQueries, B);
+        case kJacRangeBadCap:
+            return set_error(VDB_ERR_INVALID, "cap must be >= 0 and n_queries * cap <= %lld, got cap %lld for %d queries",
+                             (long long)kRangeMaxSlots, (long long)cap, B);
+        case kJacRangeBadMem: return set_error(VDB_ERR_INVALID, "bad mem kind %d", mem);
+        case kJacRangeNullPointer: return set_error(VDB_ERR_INVALID, "NULL query/threshold/count pointer");
+        case kJacRangeNullLists:
+            return set_error(VDB_ERR_INVALID, "out_indices, out_inter and out_union are required when cap > 0");
+        case kJacRangeBadThreshold:
+            return set_error(VDB_ERR_INVALID, "threshold %lld is %d / %d: it needs 1 <= den <= %d and 0 <= num <= den",
+                             (long long)at, thr_num[at], thr_den[at], kJacRangeMaxDen);
+        default: break;
+    }
+    if (B == 0) return VDB_OK;
+    const bool host = mem == VDB_MEM_HOST;
+    // as vdb_index_search_hamming_range: the caller's stream (device memory: NULL = the null stream), or
+    // for a host-memory call without one the stream of the workspace it takes
+    SearchLease lease(ix, mem, stream);
+    if (lease.rc) return lease.rc;
+    Workspace* const w = lease.w;
+    const hipStream_t st = lease.st;
+
+    const bool masked = row_mask != nullptr && N > 0;
+    const int n_bytes = ix->code_bytes;
+    const int W = ham_words(n_bytes);
+    // which scan serves the call (vdb_jaccard_range_plan.h): the scratch holds that scan's query block
+    const bool mfma = jaccard_range_use_mfma(ix->jaccard_range_mfma, B);
+    const int block = jac_range_block(mfma, B, W);
+    const JacRangeScratch sc = jaccard_range_scratch(B, n_bytes, block, N, cap, host, masked);
+    int rc = ws_reserve(w, (size_t)sc.total, st);
+    if (rc) return rc;
+    char* dev = w->dev;
+    JacRangeArgs a{};
+    a.queries = queries;
+    a.thr_num = thr_num;
+    a.thr_den = thr_den;
+    a.mask = masked ? row_mask : nullptr;
+    a.out_c = out_counts;
+    a.out_i = out_indices;
+    a.out_n = out_inter;
+    a.out_u = out_union;
+    if (host) {  // the arguments go up in one copy through the pinned staging, the results come down in one
+        rc = stage_up(w, sc.in0, sc.in_bytes, sc.out_bytes, st, [&](char* h) {
+            std::memcpy(h + (sc.q - sc.in0), queries, (size_t)B * n_bytes);
+            std::memcpy(h + (sc.num - sc.in0), thr_num, (size_t)B * 4);
+            std::memcpy(h + (sc.den - sc.in0), thr_den, (size_t)B * 4);
+            if (masked) std::memcpy(h + (sc.mask - sc.in0), row_mask, (size_t)sc.n_words * 4);
+        });
+        if (rc) return rc;
+        a.queries = reinterpret_cast<const uint8_t*>(dev + sc.q);
+        a.thr_num = reinterpret_cast<const int32_t*>(dev + sc.num);
+        a.thr_den = reinterpret_cast<const int32_t*>(dev + sc.den);
+        a.mask = masked ? reinterpret_cast<const uint32_t*>(dev + sc.mask) : nullptr;
+        a.out_c = reinterpret_cast<int64_t*>(dev + sc.out_c);
+        a.out_i = reinterpret_cast<int64_t*>(dev + sc.out_i);
+        a.out_n = reinterpret_cast<int32_t*>(dev + sc.out_n);
+        a.out_u = reinterpret_cast<int32_t*>(dev + sc.out_u);
+    }
+    if (cap == 0) a.out_i = nullptr, a.out_n = nullptr, a.out_u = nullptr;
+    if (N == 0) {  // an empty index: counts 0 and every slot -1 / -1 / -1
+        HIP_TRY(launch_jaccard_range_empty(a.out_c, B, a.out_i, a.out_n, a.out_u, cap, st));
+    } else {
+        a.codes = ix->codes;
+        a.N = N;
+        a.n_bytes = n_bytes;
+        a.W = W;
+        a.H = reinterpret_cast<uint32_t*>(dev + sc.H);
+        a.part = reinterpret_cast<uint32_t*>(dev + sc.part);
+        a.cnt = reinterpret_cast<int64_t*>(dev + sc.cnt);
+        a.cap = cap;
+        a.index_offset = index_offset;
+        // block after block on this stream over the same scratch
+        for (int b0 = 0; b0 < B; b0 += block) HIP_TRY(launch_jaccard_range_block(a, mfma, block, b0, std::min(block, B - b0), st));
+    }
+    if (host) {
+        const char* r = nullptr;
+        rc = stage_down(w, sc.in_bytes, sc.out0, sc.out_bytes, st, &r);
+        if (rc) return rc;
+        std::memcpy(out_counts, r + (sc.out_c - sc.out0), (size_t)B * 8);
+        if (cap > 0) {
+            std::memcpy(out_indices, r + (sc.out_i - sc.out0), (size_t)B * cap * 8);
+            std::memcpy(out_inter, r + (sc.out_n - sc.out0), (size_t)B * cap * 4);
+            std::memcpy(out_union, r + (sc.out_u - sc.out0), (size_t)B * cap * 4);
+        }
+    }
+    ix->n_jaccard_range_searches++;
+    ix->n_jaccard_range_queries += B;
+    if (mfma) {
+        ix->n_jaccard_range_mfma_searches++;
+        ix->n_jaccard_range_mfma_queries += B;
     }
     return VDB_OK;
 }

@@ -594,6 +594,26 @@ hipError_t launch_hamming_range_block(const HamRangeArgs& a, bool mfma, int bloc
 // An empty index: counts 0 and, with cap > 0, -1 / -1 in every slot.
 hipError_t launch_hamming_range_empty(int64_t* out_c, int n_queries, int64_t* out_i, int32_t* out_d, int64_t cap,
                                       hipStream_t st);
+// Jaccard range search (vdb_jaccard_range.hip, vdb_index_search_jaccard_range): queries [b0, b0 + qb) of
+// the batch (qb at most `block`, vdb_jaccard_range_plan.h jac_range_block) against rows [0, N), N >= 1.
+// With i = popcount(queries[b] AND row) and u = popcount(queries[b] OR row) (1 / 1 when u == 0), row r
+// passes query b when i * thr_den[b] >= thr_num[b] * u and mask (optional, the row_mask layout) has its
+// bit; a threshold outside the contract (jac_range_bad_threshold) passes nothing.  out_c[b] = the exact
+// number of passing rows; with cap > 0 the first min(count, cap) of them in ascending row order go to
+// out_i / out_n (i) / out_u (u, the raw popcounts) [b][cap] and the slots after them get -1 / -1 / -1;
+// nothing at or past cap is written.  Scan (popcount or MFMA, the same H and part in every byte), the
+// dense range search's prefix and emit, and with cap > 0 the fill, over the scratch H [block][n_words],
+// part [block][n_chunks], cnt [block], which the next block of the same stream reuses.
+struct JacRangeArgs {
+    const uint64_t* codes; int64_t N; int n_bytes; int W;
+    const uint8_t* queries; const int32_t* thr_num; const int32_t* thr_den; const uint32_t* mask;
+    uint32_t* H; uint32_t* part; int64_t* cnt;
+    int64_t cap; int64_t* out_c; int64_t* out_i; int32_t* out_n; int32_t* out_u; int64_t index_offset;
+};
+hipError_t launch_jaccard_range_block(const JacRangeArgs& a, bool mfma, int block, int b0, int qb, hipStream_t st);
+// An empty index: counts 0 and, with cap > 0, -1 / -1 / -1 in every slot.
+hipError_t launch_jaccard_range_empty(int64_t* out_c, int n_queries, int64_t* out_i, int32_t* out_n, int32_t* out_u,
+                                      int64_t cap, hipStream_t st);
 
 // Weighted-sum hybrid search (vdb_hybsum.hip, vdb_index_search_hybrid_sum).  Query b is the dense
 // vector Q[b] (qn64[b]: its canonical norm) and the sparse entries [q_indptr[b], q_indptr[b + 1]) of

@@ -58,7 +58,7 @@ EXPORTED_SYMBOLS = (
     "vdb_index_set_column", "vdb_index_filter_mask",
     "vdb_index_set_groups", "vdb_index_search_groups", "vdb_index_search_mmr", "vdb_index_search_recommend", "vdb_index_search_fused", "vdb_index_search_maxsim",
     "vdb_index_set_sparse", "vdb_index_search_sparse", "vdb_index_search_hybrid", "vdb_index_search_hybrid_sum",
-    "vdb_index_set_codes", "vdb_index_search_hamming", "vdb_index_search_hamming_range", "vdb_index_search_code_dot", "vdb_index_search_jaccard", "vdb_index_encode_codes", "vdb_index_encode", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
+    "vdb_index_set_codes", "vdb_index_search_hamming", "vdb_index_search_hamming_range", "vdb_index_search_code_dot", "vdb_index_search_jaccard", "vdb_index_search_jaccard_range", "vdb_index_encode_codes", "vdb_index_encode", "vdb_merge_topk", "vdb_similarity_matrix", "vdb_normalize_rows", "vdb_topk_scores",
     "vdb_graph_build", "vdb_graph_import", "vdb_graph_export", "vdb_graph_add", "vdb_graph_info", "vdb_graph_search",
     "vdb_graph_stat", "vdb_graph_set_param", "vdb_graph_destroy",
     "vdb_shards_create", "vdb_shards_destroy", "vdb_shards_add", "vdb_shards_count", "vdb_shards_shard_count",
@@ -150,6 +150,8 @@ def load_library():
             "vdb_index_search_jaccard": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
             "vdb_index_search_hamming_range": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64,
                                                        c_vp]),
+            "vdb_index_search_jaccard_range": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp,
+                                                       c_vp, c_i64, c_vp]),
             "vdb_index_encode_codes": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
             "vdb_index_encode": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
             "vdb_merge_topk": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
@@ -1079,6 +1081,61 @@ class NativeIndex:
             ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, int(cap), ctypes.c_void_p(out_counts_ptr or None),
             ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_dist_ptr or None), int(index_offset),
             ctypes.c_void_p(stream or None)))
+
+    def search_jaccard_range(self, queries, thr_num, thr_den, cap: Optional[int] = None, mask: Optional[np.ndarray] = None,
+                             index_offset: int = 0):
+        """include/vdb.h vdb_index_search_jaccard_range, host memory: every row whose ``mask`` bit is
+        set and whose Jaccard similarity i / u with the query is at or above the exact rational
+        ``thr_num / thr_den`` (one int32 pair per query, or scalars for all of them; 1 <= den <= 2^18,
+        0 <= num <= den, anything else raises ValueError), in ascending row id.  Returns (counts i64
+        [B], indices i64 [B, cap], intersections i32 [B, cap], unions i32 [B, cap]): counts are exact
+        even above ``cap``; slots past min(count, cap) are -1 / -1 / -1.  ``cap=0`` counts only.
+        ``cap=None``: every hit is returned -- a count-only call, then one with cap = the largest
+        count."""
+        q = self._codes(queries, "queries")
+        width = self.stat("code_bytes")
+        if q.shape[0] and width and q.shape[1] != width:
+            raise ValueError(f"queries are {q.shape[1]} bytes wide, the attached codes {width}")
+        B = q.shape[0]
+
+        def per_query(v, what):
+            v = np.asarray(v, dtype=np.int64)
+            v = np.full(B, int(v), dtype=np.int64) if v.ndim == 0 else v.reshape(-1)
+            if v.size != B:
+                raise ValueError(f"{what} needs {B} entries, got {v.size}")
+            return np.ascontiguousarray(np.clip(v, -1, 2**31 - 1), dtype=np.int32)  # (what is clipped is refused alike)
+
+        num, den = per_query(thr_num, "thr_num"), per_query(thr_den, "thr_den")
+        m, mask_p = self._mask_ptr(mask)
+
+        def call(c):
+            counts = np.zeros(B, dtype=np.int64)
+            idx = np.empty((B, max(c, 0)), dtype=np.int64)  # (a negative cap is the library's to refuse)
+            inter = np.empty((B, max(c, 0)), dtype=np.int32)
+            union = np.empty((B, max(c, 0)), dtype=np.int32)
+            _check(self._lib.vdb_index_search_jaccard_range(
+                self._h, _ptr(q) if q.size else None, B, _ptr(num) if B else None, _ptr(den) if B else None, mask_p, MEM_HOST,
+                c, _ptr(counts) if B else None, _ptr(idx) if c > 0 else None, _ptr(inter) if c > 0 else None,
+                _ptr(union) if c > 0 else None, int(index_offset), None))
+            return counts, idx, inter, union
+
+        if cap is not None:
+            return call(int(cap))
+        out = call(0)
+        most = int(out[0].max()) if B else 0
+        return call(most) if most > 0 else out
+
+    def search_jaccard_range_device(self, queries_ptr: int, n_queries: int, thr_num_ptr: int, thr_den_ptr: int, cap: int,
+                                    out_counts_ptr: int, out_idx_ptr: int = 0, out_inter_ptr: int = 0, out_union_ptr: int = 0,
+                                    mask_ptr: int = 0, index_offset: int = 0, stream: int = 0) -> None:
+        """vdb_index_search_jaccard_range with device-memory arguments (uint8 queries, int32 thresholds,
+        int64 counts and indices, int32 intersections and unions); stream-ordered, nothing is read back,
+        and a threshold outside its bounds gives its query a count of 0 (include/vdb.h)."""
+        _check(self._lib.vdb_index_search_jaccard_range(
+            self._h, ctypes.c_void_p(queries_ptr or None), int(n_queries), ctypes.c_void_p(thr_num_ptr or None),
+            ctypes.c_void_p(thr_den_ptr or None), ctypes.c_void_p(mask_ptr or None), MEM_DEVICE, int(cap),
+            ctypes.c_void_p(out_counts_ptr or None), ctypes.c_void_p(out_idx_ptr or None), ctypes.c_void_p(out_inter_ptr or None),
+            ctypes.c_void_p(out_union_ptr or None), int(index_offset), ctypes.c_void_p(stream or None)))
 
     # -- sparse and hybrid search ----------------------------------------------------
     @staticmethod

@@ -26,6 +26,8 @@ import json
 import logging
 import os
 import collections
+import fractions
+import math
 from collections import OrderedDict
 import shutil
 import threading
@@ -132,6 +134,32 @@ def normalize_code(value, what: str) -> np.ndarray:
     if not 1 <= code.size <= BINARY_MAX_BYTES:
         raise ValueError(f"{what} must hold 1..{BINARY_MAX_BYTES} bytes, got {code.size}")
     return code
+
+
+# binary_jaccard_range_query: the largest denominator of a threshold (include/vdb.h vdb_index_search_jaccard_range)
+JACCARD_MAX_DEN = 1 << 18
+
+
+def jaccard_threshold(value, n_bits: int) -> Tuple[int, int]:
+    """A similarity threshold -> the exact rational (num, den) the device compares with.  A tuple of two
+    ints is taken as it is (1 <= den <= 2^18, 0 <= num <= den).  A float t in [0, 1] is converted
+    exactly: the similarities of ``n_bits``-bit codes are the fractions of denominator <= n_bits, so t
+    passes the same rows as the smallest such fraction >= t, min over d of ceil(t d) / d in integers."""
+    if isinstance(value, tuple):
+        if len(value) != 2 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in value):
+            raise ValueError("a threshold pair is (num, den), two integers")
+        num, den = int(value[0]), int(value[1])
+        if not (1 <= den <= JACCARD_MAX_DEN and 0 <= num <= den):
+            raise ValueError(f"a threshold pair needs 1 <= den <= {JACCARD_MAX_DEN} and 0 <= num <= den, got {num} / {den}")
+        return num, den
+    t = float(value)
+    if math.isnan(t) or not 0.0 <= t <= 1.0:
+        raise ValueError(f"a similarity threshold must lie in [0, 1], got {value}")
+    f = fractions.Fraction(t)
+    best = fractions.Fraction(1)
+    for d in range(1, int(n_bits) + 1):
+        best = min(best, fractions.Fraction(-((-f.numerator * d) // f.denominator), d))
+    return best.numerator, best.denominator
 
 
 def quantize_dot_query(value, what: str = "the query") -> np.ndarray:
@@ -1795,6 +1823,82 @@ class MLXVectorStore:
                             binary_key: str = "code") -> int:
         """How many rows ``binary_range_query`` would match, from a count-only device call."""
         res = self._binary_range([code], radius, filter_metadata, binary_key, True)
+        return 0 if res is None else int(res[0][0])
+
+    def _binary_jaccard_range(self, codes, thresholds, filter_metadata, binary_key: str, count_only: bool):
+        """One vdb_index_search_jaccard_range call for a list of codes -> (counts, indices, intersections,
+        unions), or None when nothing can match (an empty store, a filter nothing passes, no row with a
+        code).  ``thresholds``: a float or a (num, den) tuple for all queries, or a list of one per query."""
+        if len(self._devices()) > 1:
+            raise NotImplementedError("binary Jaccard range query is not supported on a multi-device store")
+        qs = [normalize_code(c, "the query's code") for c in codes]
+        ts = list(thresholds) if isinstance(thresholds, list) else [thresholds] * len(qs)
+        if len(ts) != len(qs):
+            raise ValueError(f"{len(qs)} codes but {len(ts)} thresholds")
+        for t in ts:  # (refused whatever the store holds; the width decides the fraction below)
+            jaccard_threshold(t, 1)
+        with _Read(self._rw):
+            if self._vector_count == 0 or not qs:
+                return None
+            mask = self._sparse_mask(filter_metadata)
+            if mask is False:
+                return None
+            with self._code_lock:  # one attached column: attach and search as one step
+                n_bytes = self._attach_codes(binary_key)
+                if n_bytes == 0:
+                    return None
+                for q in qs:
+                    if q.size != n_bytes:
+                        raise ValueError(f"the query's code holds {q.size} bytes, the stored codes {n_bytes}")
+                pairs = [jaccard_threshold(t, 8 * n_bytes) for t in ts]
+                have = self._code_mask
+                mask = have if mask is None else (np.asarray(mask, np.uint32)[:have.size] & have)
+                return self._index.search_jaccard_range(np.stack(qs), [p[0] for p in pairs], [p[1] for p in pairs],
+                                                        cap=0 if count_only else None, mask=mask)
+
+    def binary_jaccard_range_query(self, code, threshold, filter_metadata: Optional[Dict] = None, binary_key: str = "code",
+                                   limit: Optional[int] = None) -> Tuple:
+        """Every row whose binary code (metadata key ``binary_key``, as ``binary_query`` reads it), taken
+        as a set of bits, has a Jaccard / Tanimoto similarity with ``code`` of at least ``threshold`` ->
+        (indices, hits, metadata, count), most similar first, ties to the lower row id; a row without a
+        code never matches.  ``threshold``: a float in [0, 1], converted exactly, or an exact (num, den)
+        tuple (``jaccard_threshold``).  Each hit is ``{"intersection", "union", "similarity"}``; two empty
+        sets are identical (0 / 0, similarity 1.0).  ``count`` is the exact number of rows at or above the
+        threshold; ``limit`` keeps the most similar ``limit`` of them.  Exact, on the device, and not
+        capped at 1024 results as ``binary_jaccard_query`` is (include/vdb.h
+        vdb_index_search_jaccard_range).  The reference has no such read."""
+        return self.batch_binary_jaccard_range_query([code], threshold, filter_metadata, binary_key, limit)[0]
+
+    def batch_binary_jaccard_range_query(self, codes, thresholds, filter_metadata: Optional[Dict] = None,
+                                         binary_key: str = "code", limit: Optional[int] = None) -> List[Tuple]:
+        """``binary_jaccard_range_query`` for a list of codes from one device call per pass: one tuple
+        per query.  ``thresholds``: a list of one per query, or a single one for all."""
+        if limit is not None and int(limit) < 0:
+            raise ValueError(f"limit must be >= 0, got {limit}")
+        codes = list(codes)
+        res = self._binary_jaccard_range(codes, thresholds, filter_metadata, binary_key, False)
+        if res is None:
+            return [([], [], [], 0) for _ in codes]
+        counts, idx, inter, union = res
+        meta = self._metadata
+        out = []
+        for b in range(len(codes)):
+            n = int(min(counts[b], idx.shape[1]))
+            rows = idx[b, :n].tolist()
+            ii, uu = inter[b, :n].tolist(), union[b, :n].tolist()
+            # similarity descending as an exact rational, then row ascending (the rows come ascending)
+            order = sorted(range(n), key=lambda e: -fractions.Fraction(ii[e], uu[e]) if uu[e] else -1)
+            if limit is not None:
+                order = order[:int(limit)]
+            ib = [rows[e] for e in order]
+            hits = [{"intersection": ii[e], "union": uu[e], "similarity": ii[e] / uu[e] if uu[e] else 1.0} for e in order]
+            out.append((ib, hits, [meta[i] if i < len(meta) else {} for i in ib], int(counts[b])))
+        return out
+
+    def count_binary_jaccard_within(self, code, threshold, filter_metadata: Optional[Dict] = None,
+                                    binary_key: str = "code") -> int:
+        """How many rows ``binary_jaccard_range_query`` would match, from a count-only device call."""
+        res = self._binary_jaccard_range([code], threshold, filter_metadata, binary_key, True)
         return 0 if res is None else int(res[0][0])
 
     # ---- sparse and hybrid query ----------------------------------------------------------
